@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """bench.py — driver-contract benchmark: gradient updates/sec (whole node).
 
-``python bench.py --gpus N --steps K --warmup W [--model M]``
+``python bench.py --gpus N --steps K --warmup W [--model M] [--full]
+[--dump-outputs DIR]``
 
 A *step* is one applied gradient update at the parameter server (the
 reference's iteration ``k``, SparkASGDThread.scala:199). W warmup updates run
@@ -15,6 +16,17 @@ stays FIXED as N grows (sharded over ranks) => strong scaling, matching the
 reference's fixed-dataset/more-partitions semantics. The other BASELINE
 configs (1,3,4,5) are selectable via --model (single-node; N>1 supports the
 flagship ASGD/ASAGA models, dense and CSR).
+
+A plain run does only what the headline figure needs: set up, warm up, time
+the K steps, print the result line. ``--full`` additionally measures the
+BASELINE metric's second clause (wall-clock-to-target-loss: an objective
+sweep of the optVars snapshots over the whole dataset after the run);
+without it ``config.wall_clock_to_target_loss`` is null. ``--dump-outputs
+DIR`` writes what the timed path returned to its caller (final weights
+``w.npy`` and, where the path records them, the optVars weight snapshots
+``opt_vars.npy``) as float32 .npy files after the timed steps; inputs are
+seeded, so two builds can be compared output for output (the engines are
+asynchronous, so outputs agree to optimisation noise, not bitwise).
 """
 
 from __future__ import annotations
@@ -25,6 +37,7 @@ import os
 import sys
 import time
 
+import numpy as np
 import torch
 
 from asyncframework_amd import run as runner
@@ -93,6 +106,13 @@ def parse_args():
                    choices=["", "python", "native"],
                    help="N>1 control plane: python (default) or the C++ "
                         "server (also via ASYNCAMD_DIST_ENGINE=native)")
+    p.add_argument("--full", action="store_true",
+                   help="also measure everything beyond the headline "
+                        "figure (wall-clock-to-target-loss objective "
+                        "sweep); off by default")
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="write the timed path's outputs (final weights, "
+                        "optVars snapshots) as DIR/<name>.npy")
     args = p.parse_args()
     # marks record at exact post-increment update counts, so k=0 is
     # unreachable: clamp to >=1 warmup step (negligible) rather than fail
@@ -175,6 +195,38 @@ def to_target_summary(args, data, opt_vars, target_frac: float = 0.5):
             "n_snapshots": len(obj)}
 
 
+DUMP_BUDGET_BYTES = 64 << 20  # cap on everything --dump-outputs writes
+
+
+def _sample_to_budget(a: np.ndarray, budget: int) -> np.ndarray:
+    """Whole array if it fits the byte budget, else a fixed seeded sample
+    of its elements (same indices every run, so dumps stay comparable)."""
+    if a.nbytes <= budget:
+        return a
+    n = max(1, budget // a.itemsize)
+    idx = np.sort(np.random.default_rng(0).choice(a.size, n, replace=False))
+    return a.reshape(-1)[idx]
+
+
+def dump_outputs(args, w, opt_vars=None) -> None:
+    """--dump-outputs: what the timed path handed back after its last step
+    — the final weight vector and, where recorded, the optVars weight
+    snapshots — as float32 .npy files (snapshot wall stamps are timing,
+    not output, and are left out)."""
+    if not args.dump_outputs:
+        return
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    arrays = {"w": w.detach().float().cpu().numpy()}
+    if opt_vars:
+        arrays["opt_vars"] = torch.stack(
+            [v.detach().float().cpu() for _, v in opt_vars]).numpy()
+    budget = DUMP_BUDGET_BYTES // len(arrays)
+    for name, a in arrays.items():
+        np.save(os.path.join(args.dump_outputs, name + ".npy"),
+                _sample_to_budget(np.ascontiguousarray(a, np.float32),
+                                  budget))
+
+
 def emit(args, cfg, elapsed: float, n_gpus: int, to_target=None):
     ups = args.steps / elapsed
     out = {
@@ -184,7 +236,7 @@ def emit(args, cfg, elapsed: float, n_gpus: int, to_target=None):
         "n_gpus": n_gpus,
         "steps": args.steps,
         "warmup": args.warmup,
-        "ms_per_step": round(elapsed * 1000.0 / args.steps, 4),
+        "ms_per_step": round(elapsed * 1000.0 / args.steps, 6),
         "higher_is_better": True,
         "scaling": "strong",
         "vs_baseline": None,
@@ -201,8 +253,9 @@ def emit(args, cfg, elapsed: float, n_gpus: int, to_target=None):
             "parallelism": ("sync" if args.sync else "async-ps") +
                            f"-dp{n_gpus}-w{cfg.num_workers}",
             # BASELINE.json's metric second clause, measured IN THIS RUN
-            # from the optVars snapshot ring (None only where a path has no
-            # snapshot support, e.g. N>1 rank-sharded data):
+            # from the optVars snapshot ring under --full (None in a plain
+            # run and where a path has no snapshot support, e.g. N>1
+            # rank-sharded data):
             "wall_clock_to_target_loss": to_target,
         },
     }
@@ -264,7 +317,9 @@ def run_single(args, device):
             neng = NativeLocalEngine(cfg, shards, device)
             elapsed, res = neng.bench(args.warmup, args.steps,
                                       snapshot_every=snap_cadence(args))
-        tt = to_target_summary(args, data, res.get("opt_vars"))
+        dump_outputs(args, neng.w, res.get("opt_vars"))
+        tt = (to_target_summary(args, data, res.get("opt_vars"))
+              if args.full else None)
         emit(args, cfg, elapsed, n_gpus=1, to_target=tt)
         return
 
@@ -278,6 +333,7 @@ def run_single(args, device):
         eng = GraphEngine(cfg, sh, device)
         torch.cuda.synchronize()
         t0, t1 = eng.bench(args.warmup, args.steps)
+        dump_outputs(args, eng.w)
         emit(args, cfg, t1 - t0, n_gpus=1)
         return
 
@@ -303,7 +359,9 @@ def run_single(args, device):
     if t0 is None or t1 is None or t1 <= t0:
         print(json.dumps({"error": "marks missing"}))
         sys.exit(1)
-    tt = to_target_summary(args, data, server.opt_vars)
+    dump_outputs(args, server.w, server.opt_vars)
+    tt = (to_target_summary(args, data, server.opt_vars)
+          if args.full else None)
     emit(args, cfg, t1 - t0, n_gpus=1, to_target=tt)
 
 
@@ -366,6 +424,7 @@ def run_dist(args, device, rank, world):
             if t0 is None or t1 is None or t1 <= t0:
                 print(json.dumps({"error": "marks missing"}))
             else:
+                dump_outputs(args, res.w)
                 emit(args, cfg, t1 - t0, n_gpus=world)
         dist.destroy_process_group()
         return
@@ -383,6 +442,7 @@ def run_dist(args, device, rank, world):
         if t0 is None or t1 is None or t1 <= t0:
             print(json.dumps({"error": "marks missing"}))
         else:
+            dump_outputs(args, server.w)
             emit(args, cfg, t1 - t0, n_gpus=world)
     else:
         deng.worker_loop()

@@ -17,7 +17,8 @@ REQUIRED = ["metric", "value", "unit", "n_gpus", "steps", "warmup",
 
 def _run(args):
     out = subprocess.run([sys.executable, "bench.py"] + args,
-                         capture_output=True, text=True, timeout=300)
+                         capture_output=True, text=True, timeout=300,
+                         cwd=ROOT)
     assert out.returncode == 0, out.stderr[-1500:]
     return json.loads(out.stdout.strip().splitlines()[-1])
 
@@ -31,6 +32,39 @@ def test_sync_tiny_cpu_contract():
     assert j["steps"] == 25 and j["warmup"] == 5
     assert j["data"] == "synthetic"
     assert j["config"]["model"] == "sync-tiny-cpu"
+    assert j["ms_per_step"] > 0
+    # a plain run measures the headline figure only
+    assert j["config"]["wall_clock_to_target_loss"] is None
+
+
+def test_full_and_dump_outputs_cpu(tmp_path):
+    """--full adds the to-target clause; --dump-outputs writes the timed
+    path's outputs (final weights + optVars snapshots) as float32 .npy."""
+    import numpy as np
+    d = tmp_path / "dump"
+    j = _run(["--model", "sync-tiny-cpu", "--steps", "25", "--warmup", "5",
+              "--full", "--dump-outputs", str(d)])
+    assert j["steps"] == 25 and j["ms_per_step"] > 0
+    tt = j["config"]["wall_clock_to_target_loss"]
+    assert tt is not None and tt["n_snapshots"] >= 2
+    assert tt["obj_final"] < tt["obj_initial"]
+    w = np.load(d / "w.npy")
+    assert w.dtype == np.float32 and w.shape == (784,)
+    assert np.isfinite(w).all() and np.abs(w).max() > 0
+    ov = np.load(d / "opt_vars.npy")
+    assert ov.dtype == np.float32 and ov.shape == (tt["n_snapshots"], 784)
+
+
+def test_dump_sample_is_fixed_and_bounded():
+    import numpy as np
+
+    import bench
+    a = np.arange(1000, dtype=np.float32).reshape(10, 100)
+    assert bench._sample_to_budget(a, a.nbytes) is a
+    s1 = bench._sample_to_budget(a, 400)
+    s2 = bench._sample_to_budget(a.copy(), 400)
+    assert s1.nbytes <= 400 and s1.size == 100
+    assert np.array_equal(s1, s2)
 
 
 def test_async_cpu_contract():

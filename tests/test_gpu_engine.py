@@ -2,6 +2,7 @@
 kernels, history spill config, and a bench smoke."""
 
 import json
+import os
 import subprocess
 import sys
 
@@ -90,7 +91,8 @@ def test_bench_smoke():
     out = subprocess.run(
         [sys.executable, "bench.py", "--rows", "200000", "--steps", "50",
          "--warmup", "10"],
-        capture_output=True, text=True, timeout=120)
+        capture_output=True, text=True, timeout=120,
+        cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     assert out.returncode == 0, out.stderr[-2000:]
     line = out.stdout.strip().splitlines()[-1]
     j = json.loads(line)
