@@ -54,7 +54,10 @@ def _engine_flags(p: argparse.ArgumentParser) -> None:
     p.add_argument("--max-wall-s", type=float, default=None)
     p.add_argument("--engine", default="threads",
                    choices=["threads", "native"],
-                   help="native = C++ event-loop engine (GPU, async only)")
+                   help="native = C++ engine (GPU only): async event loop, "
+                        "or stream-ordered barrier rounds for the sync "
+                        "drivers (single process; async only under "
+                        "torchrun)")
     p.add_argument("--worker-timeout-s", type=float, default=0.0,
                    help="declare a busy worker dead after this many seconds "
                         "(0 = off; the reference leaves lost workers busy "
@@ -257,5 +260,6 @@ def sgd_mllib(argv: Optional[List[str]] = None) -> None:
         workers = runner.build_csr_workers(cfg, *data)
     else:
         workers = runner.build_dense_workers(cfg, *data)
-    res, _ = runner.run_engine(cfg, workers, max_wall_s=a.max_wall_s)
+    res, _ = runner.run_engine(cfg, workers, max_wall_s=a.max_wall_s,
+                               engine=a.engine)
     runner.final_report(cfg, res, data, a.sparse, device=a.device)

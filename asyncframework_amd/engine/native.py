@@ -9,7 +9,14 @@ wave) -> pinned-flag poll -> tau filter -> batched fused update ->
 quorum-gated redispatch, including the reference's straggler model and
 calibration (csrc/engine_native.cpp header for the measured evolution).
 Use for GPU multi-worker configs (the threaded Python engine stays for
-CPU tests and as the semantics oracle)."""
+CPU tests and as the semantics oracle).
+
+``cfg.sync`` selects the engine's separate synchronous path
+(``native_sync_run``; algo asgd | asaga | mllib): one stream-ordered round
+per iteration — gradient wave over all P workers reading ``w`` itself, one
+fused round-update kernel, one host wait — with the same straggler model
+as SyncEngine + DelayInjector. Workers own no weight-snapshot buffer
+there, and the SAGA history must be device-resident."""
 
 from __future__ import annotations
 
@@ -22,14 +29,22 @@ from .worker import Shard
 
 _OBJ = {"lsq": 0, "logistic": 1}
 _ALGO = {"asgd": 0, "asaga": 1}
+_SYNC_MODE = {"asgd": 0, "asaga": 1, "mllib": 2}
 
 
 class NativeLocalEngine:
     def __init__(self, cfg: EngineConfig, shards: List[Shard],
                  device: torch.device):
+        # configuration errors first: nothing is imported or allocated yet
+        if cfg.sync:
+            assert cfg.algo in _SYNC_MODE, (
+                f"native sync engine: unknown algo {cfg.algo!r}")
+            assert cfg.history_placement != "host", (
+                "native sync engine keeps the SAGA history on the device: "
+                "history_placement='host' (spill) is async-only")
+        assert device.type == "cuda", "native engine is GPU-only"
         from .. import _hip_core
         self._core = _hip_core
-        assert device.type == "cuda", "native engine is GPU-only"
         self.cfg = cfg
         self.device = device
         self.shards = shards
@@ -40,7 +55,9 @@ class NativeLocalEngine:
         self._keep = []   # keep tensors alive across the native call
         self.alpha_tables: List[torch.Tensor] = []
         for sh in shards:
-            wbuf = torch.zeros(d, dtype=torch.float32, device=device)
+            # sync mode: every worker reads w itself (no snapshot buffer)
+            wbuf = self.w if cfg.sync else torch.zeros(
+                d, dtype=torch.float32, device=device)
             g = torch.zeros(d, dtype=torch.float32, device=device)
             ctr = torch.zeros(2, dtype=torch.int32, device=device)
             wd = dict(sparse=sh.is_sparse, y=sh.y.data_ptr(),
@@ -97,7 +114,9 @@ class NativeLocalEngine:
             snapshot_every: int = 0) -> Dict:
         """snapshot_every > 0 records (ms, w) optVars every that many
         applied updates (the reference's printer_freq loss-curve mechanism)
-        into a device ring, returned as res['opt_vars']."""
+        into a device ring, returned as res['opt_vars']. In sync mode
+        iterations, marks and the snapshot cadence count ROUNDS (one update
+        per round), as SyncEngine does."""
         cfg = self.cfg
         iters = num_iterations or cfg.num_iterations
         snap_ring = None
@@ -109,7 +128,9 @@ class NativeLocalEngine:
         conf = dict(N=cfg.N, d=cfg.d, P=cfg.num_workers, iters=iters,
                     gamma=cfg.gamma, rate=cfg.batch_rate,
                     bucket_ratio=cfg.bucket_ratio, taw=cfg.taw,
-                    seed=cfg.seed, algo=_ALGO[cfg.algo],
+                    seed=cfg.seed,
+                    algo=(int(cfg.algo == "asaga") if cfg.sync
+                          else _ALGO[cfg.algo]),
                     objective=_OBJ[cfg.objective], coeff=cfg.delay_coeff,
                     calib_window=cfg.calib_factor * cfg.num_workers,
                     mark_lo=mark_lo, mark_hi=mark_hi,
@@ -117,9 +138,15 @@ class NativeLocalEngine:
                     snap_ring=snap_ring.data_ptr() if snap_ring is not None
                     else 0, snap_cap=snap_cap)
         torch.cuda.synchronize()
-        res = self._core.native_local_run(conf, self._bufs,
-                                          self.w.data_ptr(),
-                                          self.alpha_bar.data_ptr())
+        if cfg.sync:
+            res = self._core.native_sync_run(conf, self._bufs,
+                                             self.w.data_ptr(),
+                                             self.alpha_bar.data_ptr(),
+                                             _SYNC_MODE[cfg.algo])
+        else:
+            res = self._core.native_local_run(conf, self._bufs,
+                                              self.w.data_ptr(),
+                                              self.alpha_bar.data_ptr())
         torch.cuda.synchronize()
         if snapshot_every > 0:
             snaps = res["snap_ms"]

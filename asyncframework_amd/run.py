@@ -81,24 +81,34 @@ def run_engine(cfg: EngineConfig, workers: List[Worker],
                verbose: bool = True, engine: str = "threads",
                resume_from: str = ""):
     """engine='threads' (the Python mailbox engine — CPU + semantics
-    oracle) or 'native' (the C++ event loop, GPU only, async only).
+    oracle) or 'native' (the C++ engine, GPU only: the async event loop, or
+    for ``cfg.sync`` its stream-ordered synchronous rounds).
     ``resume_from`` restores a checkpoint (threads engine only)."""
     if engine == "native":
         assert not resume_from, "resume is a threads-engine feature"
         assert not (cfg.checkpoint_every > 0 and cfg.checkpoint_path), \
             ("checkpointing with the single-GPU native engine is not wired "
              "— use --engine threads (the dist engines support it)")
+        if cfg.sync:
+            # first, before the extension is imported or anything allocated
+            assert workers[0].device.type == "cuda", \
+                "native sync engine is GPU-only"
         from .engine.native import NativeLocalEngine
-        assert not cfg.sync, "native engine is async-only"
         neng = NativeLocalEngine(cfg, [w.shard for w in workers],
                                  workers[0].device)
         nres = neng.run(max_wall_s=max_wall_s or 1800.0,
                         snapshot_every=(cfg.printer_freq
                                         if cfg.snapshot_weights else 0))
         if verbose:
+            # sync: k counts rounds — one line every printer_freq rounds,
+            # as SyncEngine prints them
             for i in range(0, nres["k"], cfg.printer_freq):
                 print(f"Iteration {i} is finished")
-        waiting = {i: int(ms) for i, ms in enumerate(nres["waiting_ms"])}
+        if cfg.sync:  # SyncEngine leaves waiting_time empty
+            waiting = {}
+        else:
+            waiting = {i: int(ms)
+                       for i, ms in enumerate(nres["waiting_ms"])}
         res = RunResult(k=int(nres["k"]), elapsed_ms=int(nres["elapsed_ms"]),
                         opt_vars=nres.get("opt_vars", []),
                         waiting_time=waiting, w=neng.w,

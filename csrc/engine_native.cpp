@@ -33,6 +33,28 @@
 // updates) -> 103k (event-free) -> 188k (wave dispatch, interleaved
 // mapping, wave-aware grid sizing). The RCCL multi-GPU server reuses this
 // loop shape with peers instead of streams (csrc/server_dist.cpp).
+//
+// Synchronous mode (run_sync; asgd-sync, asaga-sync, sgd-mllib) is a
+// SEPARATE, plain path — not the async loop with gate=P/taw=0 — so the
+// async arm and the sync arm of a comparison share one substrate (the
+// reference runs both through ASYNCreduce, SparkASGDSync.scala:239-277).
+// One round = one iteration k, everything on the ONE server stream:
+//
+//   [SAGA, k>0: commit wave of round k-1's staged history]
+//   gradient wave over ALL P slots reading w itself (no snapshot copies)
+//   [host sleeps out the straggler delay, if any]
+//   sync_round_update_kernel (fixed-order sum, step, zero g, reset
+//   counters, optional fused optVars snapshot)
+//   hipEventRecord -> host polls hipEventQuery under the stall watchdog
+//
+// Placement of the barrier: exactly ONE host wait per round, behind the
+// round's update; round k+1 is enqueued only after round k has finished
+// on the GPU. No completion flag is ever read (the gradient kernels get a
+// null done_flag), and every time that describes a round — snapshot
+// stamps, bench marks, calibration samples, elapsed — is taken after that
+// wait, so loss-curve times are completion times, not enqueue times. The
+// wall cap is checked between rounds (as the Python SyncEngine does); a
+// round in flight is bounded by stall_s and throws with its k.
 
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
@@ -49,6 +71,7 @@
 #include <deque>
 #include <stdexcept>
 #include <string>
+#include <thread>
 #include <vector>
 
 namespace py = pybind11;
@@ -115,6 +138,9 @@ void launch_scan_rows(const float*, int*, float*, int*, const int*, long,
                       uint64_t, uint32_t, uint64_t, double, hipStream_t);
 void launch_alpha_gather(float*, const float*, const int*, const int*, int,
                          hipStream_t);
+void launch_sync_round_update(float*, float* const*, int* const*, float*,
+                              float*, int*, int, int, int, float, float,
+                              float, float, int, hipStream_t);
 }
 
 namespace {
@@ -258,6 +284,10 @@ struct NativeEngine {
   bool wave_ok = false;
   float** wbuf_tab_dev = nullptr;  // device table: worker id -> wbuf pointer
   double inv_batch = 0, inv_N = 0;
+  // synchronous mode (run_sync): sample-counter pointer table + the update
+  // kernel's counter-reset ticket
+  int** ctr_tab_dev = nullptr;
+  int* sync_ticket_dev = nullptr;
 
   void init_stragglers() {
     straggler_kind.assign(cfg.P, 0);
@@ -637,7 +667,13 @@ struct NativeEngine {
     std::vector<double> snap_ms;
   };
 
-  Result run() {
+  // Streams, completion lines, wave slot tables and pointer tables shared
+  // by run() and run_sync(). ``sync``: every worker reads the iterate w
+  // itself on the ONE server stream (no snapshot buffers, no per-worker or
+  // wave streams) and publishes no completion flag (null done_flag ->
+  // publish_done returns early; done_arr stays valid because
+  // saga_commit_wave_kernel reuses it as its per-slot ticket).
+  void setup_tables(bool sync) {
     HIP_CHECK(hipStreamCreateWithFlags(&sstream, hipStreamNonBlocking));
     HIP_CHECK(hipEventCreateWithFlags(&update_ev, hipEventDisableTiming));
     HIP_CHECK(hipEventRecord(update_ev, sstream));
@@ -645,22 +681,28 @@ struct NativeEngine {
     // kernel writes it with a system-scope release; default hipHostMalloc
     // memory is fine-grained coherent on MI355X) + one padded device
     // arrival counter per worker
-    HIP_CHECK(hipHostMalloc((void**)&flags_host,
-                            (size_t)cfg.P * 16 * sizeof(unsigned long long),
-                            hipHostMallocDefault));
-    memset((void*)flags_host, 0,
-           (size_t)cfg.P * 16 * sizeof(unsigned long long));
+    if (!sync) {
+      HIP_CHECK(hipHostMalloc((void**)&flags_host,
+                              (size_t)cfg.P * 16 * sizeof(unsigned long long),
+                              hipHostMallocDefault));
+      memset((void*)flags_host, 0,
+             (size_t)cfg.P * 16 * sizeof(unsigned long long));
+    }
     HIP_CHECK(hipMalloc((void**)&arr_dev,
                         (size_t)cfg.P * 16 * sizeof(unsigned long long)));
     HIP_CHECK(hipMemset(arr_dev, 0,
                         (size_t)cfg.P * 16 * sizeof(unsigned long long)));
     for (int i = 0; i < cfg.P; ++i) {
-      ws[i].done_flag = flags_host + (size_t)i * 16;
+      ws[i].done_flag = sync ? nullptr : flags_host + (size_t)i * 16;
       ws[i].done_arr = arr_dev + (size_t)i * 16;
       ws[i].round_serial = 0;
+      if (sync) ws[i].wbuf = w;
     }
     for (auto& wk : ws) {
-      HIP_CHECK(hipStreamCreateWithFlags(&wk.stream, hipStreamNonBlocking));
+      if (sync)
+        wk.stream = sstream;
+      else
+        HIP_CHECK(hipStreamCreateWithFlags(&wk.stream, hipStreamNonBlocking));
     }
     // wave dispatch tables. Dense: ASGD pipe-kernel shapes. CSR: ASGD and
     // SAGA with device-resident history (spill mode keeps per-worker
@@ -745,9 +787,10 @@ struct NativeEngine {
                             sizeof(CommitSlot) * cfg.P,
                             hipMemcpyHostToDevice));
       }
-      for (int i = 0; i < NWSTREAM; ++i)
-        HIP_CHECK(hipStreamCreateWithFlags(&wstreams[i],
-                                           hipStreamNonBlocking));
+      if (!sync)
+        for (int i = 0; i < NWSTREAM; ++i)
+          HIP_CHECK(hipStreamCreateWithFlags(&wstreams[i],
+                                             hipStreamNonBlocking));
       wave_bper = query_grad_grid(wave_max_rows);
       if (!std::getenv("ASYNCAMD_GRAD_GRID")) {
         // measured (flagship, P=32): with interleaved full-P waves the
@@ -778,7 +821,68 @@ struct NativeEngine {
       HIP_CHECK(hipMemcpy(wbuf_tab_dev, hw.data(), cfg.P * sizeof(float*),
                           hipMemcpyHostToDevice));
     }
+    if (sync) {  // sample-counter table + reset ticket (sync_round_update)
+      std::vector<int*> hc(cfg.P);
+      for (int i = 0; i < cfg.P; ++i) hc[i] = (int*)ws[i].ctr;
+      HIP_CHECK(hipMalloc(&ctr_tab_dev, cfg.P * sizeof(int*)));
+      HIP_CHECK(hipMemcpy(ctr_tab_dev, hc.data(), cfg.P * sizeof(int*),
+                          hipMemcpyHostToDevice));
+      HIP_CHECK(hipMalloc(&sync_ticket_dev, 16));
+      HIP_CHECK(hipMemset(sync_ticket_dev, 0, 16));
+    }
     init_stragglers();
+  }
+
+  // Frees everything setup_tables made. The caller has drained every
+  // stream that may still touch these buffers.
+  void teardown_tables() {
+    for (auto& wk : ws) {
+      if (wk.stream && wk.stream != sstream)
+        HIP_CHECK(hipStreamDestroy(wk.stream));
+      wk.stream = nullptr;
+      wk.done_flag = nullptr;
+      wk.done_arr = nullptr;
+    }
+    if (flags_host) {
+      HIP_CHECK(hipHostFree((void*)flags_host));
+      flags_host = nullptr;
+    }
+    HIP_CHECK(hipFree(arr_dev));
+    arr_dev = nullptr;
+    if (slots_dev) {
+      HIP_CHECK(hipFree(slots_dev));
+      slots_dev = nullptr;
+    }
+    if (csr_slots_dev) {
+      HIP_CHECK(hipFree(csr_slots_dev));
+      csr_slots_dev = nullptr;
+    }
+    if (commit_slots_dev) {
+      HIP_CHECK(hipFree(commit_slots_dev));
+      commit_slots_dev = nullptr;
+    }
+    for (int i = 0; i < NWSTREAM; ++i)
+      if (wstreams[i]) {
+        HIP_CHECK(hipStreamDestroy(wstreams[i]));
+        wstreams[i] = nullptr;
+      }
+    HIP_CHECK(hipEventDestroy(update_ev));
+    HIP_CHECK(hipStreamDestroy(sstream));
+    HIP_CHECK(hipFree(g_tab_dev));
+    HIP_CHECK(hipFree(wbuf_tab_dev));
+    g_tab_dev = wbuf_tab_dev = nullptr;
+    if (ctr_tab_dev) {
+      HIP_CHECK(hipFree(ctr_tab_dev));
+      ctr_tab_dev = nullptr;
+    }
+    if (sync_ticket_dev) {
+      HIP_CHECK(hipFree(sync_ticket_dev));
+      sync_ticket_dev = nullptr;
+    }
+  }
+
+  Result run() {
+    setup_tables(false);
     for (int i = 0; i < cfg.P; ++i) pendingq.push_back(i);
     const double t0 = now_s();
     run_t0 = t0;
@@ -879,40 +983,253 @@ struct NativeEngine {
     out.avg_delay = avg_delay_ms;
     out.snap_ms = snap_ms;
     for (auto& wk : ws) out.waits.push_back(wk.waiting_ms);
-    for (auto& wk : ws) {
-      HIP_CHECK(hipStreamDestroy(wk.stream));
-      wk.done_flag = nullptr;
-      wk.done_arr = nullptr;
-    }
-    HIP_CHECK(hipHostFree((void*)flags_host));
-    flags_host = nullptr;
-    HIP_CHECK(hipFree(arr_dev));
-    arr_dev = nullptr;
-    if (slots_dev) {
-      HIP_CHECK(hipFree(slots_dev));
-      slots_dev = nullptr;
-    }
-    if (csr_slots_dev) {
-      HIP_CHECK(hipFree(csr_slots_dev));
-      csr_slots_dev = nullptr;
-    }
-    if (commit_slots_dev) {
-      HIP_CHECK(hipFree(commit_slots_dev));
-      commit_slots_dev = nullptr;
-    }
-    for (int i = 0; i < NWSTREAM; ++i)
-      if (wstreams[i]) {
-        HIP_CHECK(hipStreamDestroy(wstreams[i]));
-        wstreams[i] = nullptr;
+    teardown_tables();
+    return out;
+  }
+
+  // -- synchronous mode (see the file header) ------------------------------
+
+  // Round kr's gradient work, all on the server stream: (SAGA, kr > 0) the
+  // commit of round kr-1's staged history — every sync round is accepted —
+  // then one gradient wave over ALL P slots against w itself. Shapes the
+  // wave kernels do not cover take the per-worker launch_grad on that same
+  // stream (setup_tables(true) pointed wk.stream at sstream, wk.wbuf at w).
+  void sync_enqueue_grad(long kr) {
+    const long round_key = kr + 1;  // reference seed+k+1
+    if (!wave_ok) {
+      for (auto& wk : ws) {
+        if (cfg.algo == 1 && kr > 0) {
+          launch_saga_commit_devn((float*)wk.alpha, (const int*)wk.idx_out,
+                                  (const float*)wk.e_out,
+                                  (const int*)(wk.ctr + 4), wk.saga_cap,
+                                  sstream);
+          HIP_CHECK(hipGetLastError());
+        }
+        launch_grad(wk, round_key);  // SAGA: re-zeroes ctr after the commit
       }
-    HIP_CHECK(hipEventDestroy(update_ev));
-    HIP_CHECK(hipStreamDestroy(sstream));
-    HIP_CHECK(hipFree(g_tab_dev));
-    HIP_CHECK(hipFree(wbuf_tab_dev));
-    g_tab_dev = wbuf_tab_dev = nullptr;
+      return;
+    }
+    if (cfg.algo == 1 && kr > 0) {
+      CsrCommitCmd cc{};
+      cc.n = cfg.P;
+      cc.bper = 16;
+      for (int i = 0; i < cfg.P; ++i) {
+        cc.wid[i] = i;
+        cc.do_commit[i] = 1;
+      }
+      launch_saga_commit_wave(commit_slots_dev, &cc, sstream);
+      HIP_CHECK(hipGetLastError());
+    }
+    GradWaveCmd cmd{};
+    cmd.n = cfg.P;
+    cmd.bper = wave_bper;
+    cmd.interleave = wave_interleave;
+    for (int i = 0; i < cfg.P; ++i) {
+      cmd.wid[i] = i;
+      cmd.round_k[i] = (unsigned int)round_key;
+      cmd.done_val[i] = 0;  // unused: the sync slots carry a null done_flag
+    }
+    if (slots_dev)
+      launch_grad_dense_wave(slots_dev, &cmd, wave_max_rows, cfg.d, cfg.seed,
+                             cfg.rate, cfg.objective, ws[0].x_is_bf16,
+                             cfg.algo == 1 ? 1 : 0, sstream);
+    else
+      launch_grad_csr_wave(csr_slots_dev, &cmd, cfg.seed, cfg.rate,
+                           cfg.objective, ws[0].x_is_bf16,
+                           cfg.algo == 1 ? 1 : 0, sstream);
+    HIP_CHECK(hipGetLastError());
+  }
+
+  // The barrier: poll the event recorded behind round kr's update. Bounded
+  // by the stall watchdog counted from ``t_from`` (the later of submit and
+  // straggler release) — never an unbounded synchronize.
+  void sync_wait_round(long kr, double t_from) {
+    const double deadline = t_from + cfg.stall_s;
+    while (true) {
+      const hipError_t e = hipEventQuery(update_ev);
+      if (e == hipSuccess) break;
+      if (e != hipErrorNotReady)
+        throw std::runtime_error(std::string("native sync engine: ") +
+                                 hipGetErrorString(e) + " at round k=" +
+                                 std::to_string(kr));
+      if (now_s() > deadline)
+        throw std::runtime_error(
+            "native sync engine stalled: round k=" + std::to_string(kr) +
+            " not complete after " + std::to_string(cfg.stall_s) + " s");
+    }
+    (void)hipGetLastError();  // drop the polls' hipErrorNotReady
+  }
+
+  // mode: 0 asgd, 1 asaga, 2 mllib (cfg.algo is 1 for asaga, else 0).
+  Result run_sync(int mode) {
+    setup_tables(true);
+    bool vec4 = cfg.d % 4 == 0 &&
+                ((w | alpha_bar | cfg.snap_ring) & 15) == 0;
+    for (auto& wk : ws) vec4 = vec4 && (wk.g & 15) == 0;
+    // start from quiescent accumulators and counters whatever an earlier
+    // run on these buffers left (its last round's SAGA staging included)
+    for (auto& wk : ws) {
+      HIP_CHECK(hipMemsetAsync((void*)wk.g, 0, (size_t)cfg.d * 4, sstream));
+      HIP_CHECK(hipMemsetAsync((void*)wk.ctr, 0, 8, sstream));
+    }
+    HIP_CHECK(hipEventRecord(update_ev, sstream));
+    sync_wait_round(-1, now_s());
+    const double inv_bN = 1.0 / (cfg.rate * (double)cfg.N);
+    inv_N = 1.0 / (double)cfg.N;
+    const double t0 = now_s();
+    run_t0 = t0;
+    double t1 = t0;
+    while (k < cfg.iters) {
+      const double t_submit = now_s();
+      if (t_submit - t0 > cfg.max_wall_s) break;
+      // delay calibration activation (DelayInjector.maybe_activate)
+      if (!delay_flag && k > cfg.calib_window) {
+        if (cul_count > 0) avg_delay_ms = cul_time_ms / cul_count;
+        delay_flag = true;
+      }
+      sync_enqueue_grad(k);
+      // straggler model: the barrier releases at max(gradient done,
+      // t_submit + slowest worker's injected delay). The gradient runs on
+      // the GPU while the host sleeps out the delay; the update is enqueued
+      // only after the release time and is stream-ordered behind the
+      // gradient, which gives the max().
+      double dly_ms = 0.0;
+      for (int wid = 0; wid < cfg.P; ++wid)
+        dly_ms = std::max(dly_ms, delay_ms_for(wid, k));
+      double t_release = t_submit;
+      if (dly_ms > 0) {
+        t_release = std::min(t_submit + dly_ms / 1000.0,
+                             t0 + cfg.max_wall_s);
+        const double left = t_release - now_s();
+        if (left > 0)
+          std::this_thread::sleep_for(std::chrono::duration<double>(left));
+      }
+      const bool snap_now = cfg.snap_every > 0 && k % cfg.snap_every == 0 &&
+                            (long)snap_ms.size() < cfg.snap_cap;
+      float* snap_dst =
+          snap_now ? (float*)(cfg.snap_ring + (uintptr_t)snap_ms.size() *
+                                                  (size_t)cfg.d * 4)
+                   : nullptr;
+      const double gamma_k = cfg.gamma / std::sqrt((double)(k + 1));
+      const float scale = mode == 0   ? (float)(gamma_k * inv_bN)
+                          : mode == 2 ? (float)gamma_k
+                                      : 0.f;
+      launch_sync_round_update((float*)w, (float* const*)g_tab_dev,
+                               (int* const*)ctr_tab_dev, (float*)alpha_bar,
+                               snap_dst, sync_ticket_dev, cfg.P, cfg.d, mode,
+                               scale, (float)cfg.gamma, (float)inv_bN,
+                               (float)inv_N, vec4 ? 1 : 0, sstream);
+      HIP_CHECK(hipGetLastError());
+      HIP_CHECK(hipEventRecord(update_ev, sstream));
+      sync_wait_round(k, std::max(t_submit, t_release));
+      // every stamp that describes round k is taken here, after the GPU
+      // has finished it
+      t1 = now_s();
+      if (k * cfg.P < cfg.calib_window) {  // DelayInjector.record_task
+        cul_time_ms += (t1 - t_submit) * 1000.0 * cfg.P;
+        cul_count += cfg.P;
+      }
+      if (snap_now) snap_ms.push_back((t1 - t0) * 1000.0);
+      k += 1;
+      applied += 1;
+      if (k == cfg.mark_lo) mark_lo_t = t1;
+      if (k == cfg.mark_hi) mark_hi_t = t1;
+    }
+    Result out;
+    out.k = k;
+    out.elapsed_ms = (t1 - t0) * 1000.0;
+    out.applied = applied;
+    out.rejected = 0;
+    out.max_staleness = 0;
+    out.mark_lo_t = mark_lo_t;
+    out.mark_hi_t = mark_hi_t;
+    out.avg_delay = avg_delay_ms;
+    out.snap_ms = snap_ms;
+    out.waits.assign(cfg.P, 0.0);
+    teardown_tables();
     return out;
   }
 };
+
+}  // namespace
+
+namespace {
+
+void fill_engine(NativeEngine& eng, py::dict c, py::list workers,
+                 uintptr_t w, uintptr_t alpha_bar) {
+  EngineCfg& cfg = eng.cfg;
+  cfg.N = py::cast<long>(c["N"]);
+  cfg.d = py::cast<int>(c["d"]);
+  cfg.P = py::cast<int>(c["P"]);
+  cfg.iters = py::cast<long>(c["iters"]);
+  cfg.gamma = py::cast<double>(c["gamma"]);
+  cfg.rate = py::cast<double>(c["rate"]);
+  cfg.bucket_ratio = py::cast<double>(c["bucket_ratio"]);
+  cfg.taw = py::cast<long>(c["taw"]);
+  cfg.seed = py::cast<uint64_t>(c["seed"]);
+  cfg.algo = py::cast<int>(c["algo"]);
+  cfg.objective = py::cast<int>(c["objective"]);
+  cfg.coeff = py::cast<double>(c["coeff"]);
+  cfg.calib_window = py::cast<long>(c["calib_window"]);
+  cfg.mark_lo = py::cast<long>(c["mark_lo"]);
+  cfg.mark_hi = py::cast<long>(c["mark_hi"]);
+  cfg.max_wall_s = py::cast<double>(c["max_wall_s"]);
+  if (c.contains("stall_s")) cfg.stall_s = py::cast<double>(c["stall_s"]);
+  cfg.snap_every = py::cast<long>(c["snap_every"]);
+  cfg.snap_ring = py::cast<uintptr_t>(c["snap_ring"]);
+  cfg.snap_cap = py::cast<long>(c["snap_cap"]);
+  for (auto item : workers) {
+    py::dict wd = py::cast<py::dict>(item);
+    WorkerBuf wk;
+    wk.sparse = py::cast<bool>(wd["sparse"]);
+    if (wk.sparse) {
+      wk.indptr = py::cast<uintptr_t>(wd["indptr"]);
+      wk.indices = py::cast<uintptr_t>(wd["indices"]);
+      wk.values = py::cast<uintptr_t>(wd["values"]);
+    } else {
+      wk.X = py::cast<uintptr_t>(wd["X"]);
+    }
+    wk.y = py::cast<uintptr_t>(wd["y"]);
+    wk.wbuf = py::cast<uintptr_t>(wd["wbuf"]);
+    wk.g = py::cast<uintptr_t>(wd["g"]);
+    wk.ctr = py::cast<uintptr_t>(wd["ctr"]);
+    wk.n_rows = py::cast<long>(wd["n_rows"]);
+    wk.row_start = py::cast<long>(wd["row_start"]);
+    wk.x_is_bf16 = py::cast<int>(wd["x_is_bf16"]);
+    if (eng.cfg.algo == 1) {
+      wk.alpha = py::cast<uintptr_t>(wd["alpha"]);
+      wk.idx_out = py::cast<uintptr_t>(wd["idx_out"]);
+      wk.e_out = py::cast<uintptr_t>(wd["e_out"]);
+      wk.saga_cap = py::cast<int>(wd["saga_cap"]);
+      if (wd.contains("alpha_host")) {
+        wk.alpha_host = py::cast<uintptr_t>(wd["alpha_host"]);
+        wk.srows = py::cast<uintptr_t>(wd["srows"]);
+        wk.sylist = py::cast<uintptr_t>(wd["sylist"]);
+        wk.scnt = py::cast<uintptr_t>(wd["scnt"]);
+      }
+    }
+    eng.ws.push_back(wk);
+  }
+  if ((int)eng.ws.size() != cfg.P)
+    throw std::runtime_error("native engine: P != len(workers)");
+  eng.w = w;
+  eng.alpha_bar = alpha_bar;
+}
+
+py::dict result_dict(const NativeEngine::Result& r) {
+  py::dict out;
+  out["k"] = r.k;
+  out["elapsed_ms"] = r.elapsed_ms;
+  out["applied"] = r.applied;
+  out["rejected"] = r.rejected;
+  out["max_staleness"] = r.max_staleness;
+  out["mark_lo_t"] = r.mark_lo_t;
+  out["mark_hi_t"] = r.mark_hi_t;
+  out["avg_delay_ms"] = r.avg_delay;
+  out["waiting_ms"] = r.waits;
+  out["snap_ms"] = r.snap_ms;
+  return out;
+}
 
 }  // namespace
 
@@ -921,80 +1238,37 @@ void register_native_engine(py::module_& m) {
       "native_local_run",
       [](py::dict c, py::list workers, uintptr_t w, uintptr_t alpha_bar) {
         NativeEngine eng;
-        EngineCfg& cfg = eng.cfg;
-        cfg.N = py::cast<long>(c["N"]);
-        cfg.d = py::cast<int>(c["d"]);
-        cfg.P = py::cast<int>(c["P"]);
-        cfg.iters = py::cast<long>(c["iters"]);
-        cfg.gamma = py::cast<double>(c["gamma"]);
-        cfg.rate = py::cast<double>(c["rate"]);
-        cfg.bucket_ratio = py::cast<double>(c["bucket_ratio"]);
-        cfg.taw = py::cast<long>(c["taw"]);
-        cfg.seed = py::cast<uint64_t>(c["seed"]);
-        cfg.algo = py::cast<int>(c["algo"]);
-        cfg.objective = py::cast<int>(c["objective"]);
-        cfg.coeff = py::cast<double>(c["coeff"]);
-        cfg.calib_window = py::cast<long>(c["calib_window"]);
-        cfg.mark_lo = py::cast<long>(c["mark_lo"]);
-        cfg.mark_hi = py::cast<long>(c["mark_hi"]);
-        cfg.max_wall_s = py::cast<double>(c["max_wall_s"]);
-        if (c.contains("stall_s"))
-          cfg.stall_s = py::cast<double>(c["stall_s"]);
-        cfg.snap_every = py::cast<long>(c["snap_every"]);
-        cfg.snap_ring = py::cast<uintptr_t>(c["snap_ring"]);
-        cfg.snap_cap = py::cast<long>(c["snap_cap"]);
-        for (auto item : workers) {
-          py::dict wd = py::cast<py::dict>(item);
-          WorkerBuf wk;
-          wk.sparse = py::cast<bool>(wd["sparse"]);
-          if (wk.sparse) {
-            wk.indptr = py::cast<uintptr_t>(wd["indptr"]);
-            wk.indices = py::cast<uintptr_t>(wd["indices"]);
-            wk.values = py::cast<uintptr_t>(wd["values"]);
-          } else {
-            wk.X = py::cast<uintptr_t>(wd["X"]);
-          }
-          wk.y = py::cast<uintptr_t>(wd["y"]);
-          wk.wbuf = py::cast<uintptr_t>(wd["wbuf"]);
-          wk.g = py::cast<uintptr_t>(wd["g"]);
-          wk.ctr = py::cast<uintptr_t>(wd["ctr"]);
-          wk.n_rows = py::cast<long>(wd["n_rows"]);
-          wk.row_start = py::cast<long>(wd["row_start"]);
-          wk.x_is_bf16 = py::cast<int>(wd["x_is_bf16"]);
-          if (eng.cfg.algo == 1) {
-            wk.alpha = py::cast<uintptr_t>(wd["alpha"]);
-            wk.idx_out = py::cast<uintptr_t>(wd["idx_out"]);
-            wk.e_out = py::cast<uintptr_t>(wd["e_out"]);
-            wk.saga_cap = py::cast<int>(wd["saga_cap"]);
-            if (wd.contains("alpha_host")) {
-              wk.alpha_host = py::cast<uintptr_t>(wd["alpha_host"]);
-              wk.srows = py::cast<uintptr_t>(wd["srows"]);
-              wk.sylist = py::cast<uintptr_t>(wd["sylist"]);
-              wk.scnt = py::cast<uintptr_t>(wd["scnt"]);
-            }
-          }
-          eng.ws.push_back(wk);
-        }
-        if ((int)eng.ws.size() != cfg.P)
-          throw std::runtime_error("native engine: P != len(workers)");
-        eng.w = w;
-        eng.alpha_bar = alpha_bar;
+        fill_engine(eng, c, workers, w, alpha_bar);
         NativeEngine::Result r;
         {
           py::gil_scoped_release rel;  // the event loop never touches Python
           r = eng.run();
         }
-        py::dict out;
-        out["k"] = r.k;
-        out["elapsed_ms"] = r.elapsed_ms;
-        out["applied"] = r.applied;
-        out["rejected"] = r.rejected;
-        out["max_staleness"] = r.max_staleness;
-        out["mark_lo_t"] = r.mark_lo_t;
-        out["mark_hi_t"] = r.mark_hi_t;
-        out["avg_delay_ms"] = r.avg_delay;
-        out["waiting_ms"] = r.waits;
-        out["snap_ms"] = r.snap_ms;
-        return out;
+        return result_dict(r);
+      });
+  // Synchronous mode: same conf/worker dicts, plus mode 0 asgd / 1 asaga /
+  // 2 mllib (conf["algo"] is 1 for asaga, else 0). Host-spill history is
+  // not supported here (the Python adapter rejects it).
+  m.def(
+      "native_sync_run",
+      [](py::dict c, py::list workers, uintptr_t w, uintptr_t alpha_bar,
+         int mode) {
+        if (mode < 0 || mode > 2)
+          throw std::runtime_error("native sync engine: mode must be 0..2");
+        NativeEngine eng;
+        fill_engine(eng, c, workers, w, alpha_bar);
+        if ((mode == 1) != (eng.cfg.algo == 1))
+          throw std::runtime_error(
+              "native sync engine: mode/algo mismatch");
+        for (auto& wk : eng.ws)
+          if (wk.alpha_host)
+            throw std::runtime_error(
+                "native sync engine: host-spill history is not supported");
+        NativeEngine::Result r;
+        {
+          py::gil_scoped_release rel;
+          r = eng.run_sync(mode);
+        }
+        return result_dict(r);
       });
 }

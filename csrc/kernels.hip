@@ -1107,6 +1107,106 @@ __global__ __launch_bounds__(256) void multi_update_kernel(
   }
 }
 
+// ------------------------------------------------------ sync round update
+// (native engine, synchronous mode): ONE kernel applies ONE barrier round.
+// multi_update_kernel cannot do this job — it applies its gradients one
+// after another (SAGA would add alpha_bar P times) and has no MLlib
+// divisor. Per element i:
+//   s = sum_p g_p[i] in FIXED worker order 0..P-1 (deterministic: the result
+//       does not depend on which worker's kernel blocks finished first);
+//   g_p[i] = 0 for all p (the next round accumulates from zero);
+//   mode 0 asgd : w -= scale * s            (scale = gamma_k / (b*N), host)
+//   mode 1 asaga: w -= gamma * (inv_batch*s + alpha_bar); alpha_bar += s/N
+//                 (w reads the OLD alpha_bar, as saga_update_kernel)
+//   mode 2 mllib: w -= scale * s / max(n,1) (scale = gamma_k, host;
+//                 n = sum_p ctr_p[0], the round's ACTUAL sample count, read
+//                 here on the device — no D2H);
+//   snap_dst[i] = post-update w[i] when snap_dst != null (fused optVars
+//                 snapshot copy).
+// Everything read here (g_p, ctr_p) was written by the gradient kernel that
+// precedes this one ON THE SAME STREAM, so plain loads are correct — unlike
+// the async path, whose cross-stream consumers need agent-scope atomics.
+// The sample counters are zeroed for the next round by the LAST block to
+// finish (atomic ticket, as sgd_reduce_update_kernel): every block has
+// already parked its counter sum in LDS before it takes a ticket, so the
+// reset races no read.
+#define SRU_BLOCK 64
+
+template <bool VEC4>
+__global__ __launch_bounds__(SRU_BLOCK) void sync_round_update_kernel(
+    float* __restrict__ w, float* const* __restrict__ g_tab,
+    int* const* __restrict__ ctr_tab, float* __restrict__ alpha_bar,
+    float* __restrict__ snap_dst, int* __restrict__ ticket, int P, int d,
+    int mode, float scale, float gamma, float inv_batch, float inv_N) {
+  __shared__ int n_sh;
+  if (mode == 2) {  // uniform per launch
+    if (threadIdx.x == 0) {
+      int n = 0;
+      for (int p = 0; p < P; ++p) n += *ctr_tab[p];
+      n_sh = n;
+    }
+    __syncthreads();
+    scale = scale / (float)max(n_sh, 1);
+  }
+  const int stride = gridDim.x * SRU_BLOCK;
+  if (VEC4) {
+    const int n4 = d >> 2;
+    for (int i = blockIdx.x * SRU_BLOCK + threadIdx.x; i < n4; i += stride) {
+      float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll 8
+      for (int p = 0; p < P; ++p) {
+        const float4 v = reinterpret_cast<const float4*>(g_tab[p])[i];
+        s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
+      }
+      for (int p = 0; p < P; ++p)
+        reinterpret_cast<float4*>(g_tab[p])[i] =
+            make_float4(0.f, 0.f, 0.f, 0.f);
+      float4 wi = reinterpret_cast<float4*>(w)[i];
+      if (mode == 1) {
+        float4 ab = reinterpret_cast<float4*>(alpha_bar)[i];
+        wi.x -= gamma * (inv_batch * s.x + ab.x);
+        wi.y -= gamma * (inv_batch * s.y + ab.y);
+        wi.z -= gamma * (inv_batch * s.z + ab.z);
+        wi.w -= gamma * (inv_batch * s.w + ab.w);
+        ab.x += inv_N * s.x; ab.y += inv_N * s.y;
+        ab.z += inv_N * s.z; ab.w += inv_N * s.w;
+        reinterpret_cast<float4*>(alpha_bar)[i] = ab;
+      } else {
+        wi.x -= scale * s.x; wi.y -= scale * s.y;
+        wi.z -= scale * s.z; wi.w -= scale * s.w;
+      }
+      reinterpret_cast<float4*>(w)[i] = wi;
+      if (snap_dst) reinterpret_cast<float4*>(snap_dst)[i] = wi;
+    }
+  } else {
+    for (int i = blockIdx.x * SRU_BLOCK + threadIdx.x; i < d; i += stride) {
+      float s = 0.f;
+#pragma unroll 8
+      for (int p = 0; p < P; ++p) s += g_tab[p][i];
+      for (int p = 0; p < P; ++p) g_tab[p][i] = 0.f;
+      float wi = w[i];
+      if (mode == 1) {
+        const float ab = alpha_bar[i];
+        wi -= gamma * (inv_batch * s + ab);
+        alpha_bar[i] = ab + inv_N * s;
+      } else {
+        wi -= scale * s;
+      }
+      w[i] = wi;
+      if (snap_dst) snap_dst[i] = wi;
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const int t = atomicAdd(ticket, 1);
+    if (t == (int)gridDim.x - 1) {
+      for (int p = 0; p < P; ++p) *ctr_tab[p] = 0;
+      (void)__hip_atomic_exchange(ticket, 0, __ATOMIC_RELAXED,
+                                  __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+}
+
 // Fused reduce+update (overlap graph mode): one kernel sums the per-block
 // partial slabs AND applies the ASGD update. Each block reads k at entry
 // (k is stable for the whole kernel); the last-finishing block (atomic
@@ -1724,6 +1824,35 @@ void launch_multi_update(float* w, float* const* g_tab,
   hipLaunchKernelGGL(multi_update_kernel, dim3(grid), dim3(256), 0, stream,
                      w, g_tab, wbuf_tab, alpha_bar, gamma, inv_batch, inv_N,
                      d, *a);
+}
+
+// One barrier round of the native engine's synchronous mode. The work is
+// d*P floats (<= ~12 MB at rcv1's d=47,236, P=64; a few KB at the dense
+// shapes), latency-bound: 64-thread blocks spread even d=784 (196 float4
+// lanes) over 4 CUs, and d=47,236 gives 185 blocks — under one per CU —
+// so the grid-stride loop only engages past d = 262,144. ``vec4`` selects
+// the float4 form (caller guarantees d % 4 == 0 and 16-byte-aligned
+// buffers).
+void launch_sync_round_update(float* w, float* const* g_tab,
+                              int* const* ctr_tab, float* alpha_bar,
+                              float* snap_dst, int* ticket, int P, int d,
+                              int mode, float scale, float gamma,
+                              float inv_batch, float inv_N, int vec4,
+                              hipStream_t stream) {
+  const int n = vec4 ? d / 4 : d;
+  int grid = (n + SRU_BLOCK - 1) / SRU_BLOCK;
+  if (grid > 1024) grid = 1024;
+  if (grid < 1) grid = 1;
+  if (vec4)
+    hipLaunchKernelGGL(sync_round_update_kernel<true>, dim3(grid),
+                       dim3(SRU_BLOCK), 0, stream, w, g_tab, ctr_tab,
+                       alpha_bar, snap_dst, ticket, P, d, mode, scale, gamma,
+                       inv_batch, inv_N);
+  else
+    hipLaunchKernelGGL(sync_round_update_kernel<false>, dim3(grid),
+                       dim3(SRU_BLOCK), 0, stream, w, g_tab, ctr_tab,
+                       alpha_bar, snap_dst, ticket, P, d, mode, scale, gamma,
+                       inv_batch, inv_N);
 }
 
 void launch_saga_commit_devn(float* alpha, const int* idx, const float* e,

@@ -18,7 +18,12 @@ production async path); the sync arm on the SyncEngine full-barrier path
 (the framework's Spark-sync analog) — matching the reference's comparison
 of its async system against the synchronous system, both under the same
 delay model on the same hardware. ``--async-engine threads`` selects the
-Python engine for an apples-to-apples control.
+Python engine for an apples-to-apples control, and ``--sync-engine native``
+runs the sync arm through the native engine's synchronous mode, so both
+arms share one control plane (the reference compares both arms on one
+substrate, SparkASGDSync.scala:239-277). The multiplier to publish is the
+same-substrate one; the default (threads sync vs native async) is
+cross-substrate.
 
 Usage: python tools/compare_async_sync.py --preset fig7-mnist8m
    or: python tools/compare_async_sync.py [--rows N] [--cols D] [...]
@@ -107,11 +112,16 @@ def main():
     p.add_argument("--calib-factor", type=int, default=10)
     p.add_argument("--target-rel", type=float, default=0.35,
                    help="target = rel * initial objective (floored at the "
-                        "worse arm's best achieved + 2%)")
+                        "worse arm's best achieved + 2%%)")
     p.add_argument("--dtype", default="fp32")
     p.add_argument("--max-wall-s", type=float, default=300.0)
     p.add_argument("--async-engine", default="",
                    choices=["", "native", "threads"])
+    p.add_argument("--sync-engine", default="threads",
+                   choices=["threads", "native"],
+                   help="sync arm substrate: the Python-threads SyncEngine "
+                        "(default) or the native engine's synchronous mode "
+                        "(same substrate as the native async arm)")
     args = p.parse_args()
     if args.preset:
         for key, v in PRESETS[args.preset].items():
@@ -145,8 +155,15 @@ def main():
             acfg, X, y, args.max_wall_s, max(1, args.iters_async // 60))
     else:
         async_curve, ak, ams = sync_loss_curve(acfg, X, y, args.max_wall_s)
-    sync_curve, sk, sms = sync_loss_curve(mk_cfg(True), X, y,
-                                          args.max_wall_s)
+    scfg = mk_cfg(True)
+    if args.sync_engine == "native":
+        # same substrate as the async arm: NativeLocalEngine dispatches a
+        # sync cfg to the engine's stream-ordered barrier rounds
+        assert on_gpu, "--sync-engine native needs a GPU device"
+        sync_curve, sk, sms = async_loss_curve_native(
+            scfg, X, y, args.max_wall_s, scfg.printer_freq)
+    else:
+        sync_curve, sk, sms = sync_loss_curve(scfg, X, y, args.max_wall_s)
 
     obj0 = async_curve[0][1]
     floor = max(min(o for _, o in async_curve),
@@ -167,7 +184,8 @@ def main():
                    "iters_async": args.iters_async,
                    "iters_sync": args.iters_sync,
                    "dtype": args.dtype, "device": args.device,
-                   "async_engine": async_engine},
+                   "async_engine": async_engine,
+                   "sync_engine": args.sync_engine},
         "initial_objective": obj0,
         "target_objective": target,
         "async": {"iters": ak, "elapsed_ms": ams,
