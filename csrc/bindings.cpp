@@ -9,11 +9,15 @@
 // the hipGraph engine (engine/graph.py).
 
 #include <pybind11/pybind11.h>
+#include <pybind11/stl.h>
 
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <stdexcept>
 #include <string>
+#include <vector>
+
+#include "multi_update.h"
 
 namespace py = pybind11;
 
@@ -57,6 +61,10 @@ void launch_sgd_update_fused(float*, float*, int*, float, float, int, int,
                              hipStream_t);
 void launch_saga_update_fused(float*, float*, float*, int*, float, float,
                               float, int, hipStream_t);
+int query_dense_kernel(int, int, int, int, int*);
+void launch_multi_update(float*, float* const*, float* const*, float*, float,
+                         float, float, int, const MultiUpdateArgs*, int,
+                         hipStream_t);
 }
 
 static void check(hipError_t err, const char* what) {
@@ -223,6 +231,90 @@ PYBIND11_MODULE(_hip_core, m) {
                                    (int*)k_dev, gamma, inv_batch, inv_N, d,
                                    (hipStream_t)stream);
           check(hipGetLastError(), "saga_update_fused launch");
+        });
+
+  // What a dense gradient launch at feature dim d will run (the launchers'
+  // own shape selection, csrc/kernels.hip): template parameters, compiled
+  // register/scratch use and the occupancy the runtime computes for them.
+  m.def("dense_kernel_info", [](int d, int x_is_bf16, int saga, int wave) {
+    int v[8] = {0};
+    const int rc = query_dense_kernel(d, x_is_bf16, saga, wave, v);
+    if (rc == -1)
+      throw std::runtime_error(
+          "dense_kernel_info: d must be a multiple of 4 in [4, 2048] (other "
+          "dims run the generic grad_dense_kernel)");
+    check((hipError_t)rc, "dense_kernel_info");
+    py::dict out;
+    out["kernel"] = wave ? "grad_dense_wave_kernel" : "grad_dense_pipe_kernel";
+    out["iters"] = v[0];
+    out["depth"] = v[1];
+    out["waves_per_simd_hint"] = v[2];
+    out["num_regs"] = v[3];
+    out["local_size_bytes"] = v[4];
+    out["dynamic_lds_bytes"] = v[5];
+    out["max_active_blocks_per_cu"] = v[6];
+    return out;
+  });
+
+  // Direct launch of the native engine's batched update kernel (tests).
+  // g_ptrs / wbuf_ptrs are the per-worker device buffers (the engine's
+  // g_tab / wbuf_tab); gw / sw index them; gw entries must be distinct.
+  // Synchronous: returns after the kernel has finished.
+  m.def("multi_update",
+        [](uintptr_t w, std::vector<uintptr_t> g_ptrs,
+           std::vector<uintptr_t> wbuf_ptrs, uintptr_t alpha_bar, float gamma,
+           float inv_batch, float inv_N, int d, int algo,
+           std::vector<int> gw, std::vector<int> sw,
+           std::vector<float> scale, uintptr_t stream) {
+          if (gw.size() > MU_MAX || sw.size() > MU_MAX)
+            throw std::runtime_error("multi_update: batch exceeds MU_MAX");
+          if (algo == 0 && scale.size() != gw.size())
+            throw std::runtime_error("multi_update: len(scale) != len(gw)");
+          MultiUpdateArgs a{};
+          a.n = (int)gw.size();
+          a.m = (int)sw.size();
+          a.algo = algo;
+          bool vec4 = d % 4 == 0 && ((w | alpha_bar) & 15) == 0;
+          for (auto p : g_ptrs) vec4 = vec4 && (p & 15) == 0;
+          for (auto p : wbuf_ptrs) vec4 = vec4 && (p & 15) == 0;
+          for (int j = 0; j < a.n; ++j) {
+            if (gw[j] < 0 || (size_t)gw[j] >= g_ptrs.size())
+              throw std::runtime_error("multi_update: gw out of range");
+            for (int q = 0; q < j; ++q)
+              if (gw[q] == gw[j])
+                throw std::runtime_error("multi_update: duplicate worker");
+            a.gw[j] = gw[j];
+            if (algo == 0) a.scale[j] = scale[j];
+          }
+          for (int j = 0; j < a.m; ++j) {
+            if (sw[j] < 0 || (size_t)sw[j] >= wbuf_ptrs.size())
+              throw std::runtime_error("multi_update: sw out of range");
+            a.sw[j] = sw[j];
+          }
+          void* tabs = nullptr;
+          const size_t ng = g_ptrs.size(), nw = wbuf_ptrs.size();
+          check(hipMalloc(&tabs, (ng + nw + 1) * sizeof(uintptr_t)),
+                "multi_update tables");
+          uintptr_t* g_tab = (uintptr_t*)tabs;
+          uintptr_t* wbuf_tab = g_tab + ng;
+          hipError_t e = hipSuccess;
+          if (ng)
+            e = hipMemcpy(g_tab, g_ptrs.data(), ng * sizeof(uintptr_t),
+                          hipMemcpyHostToDevice);
+          if (e == hipSuccess && nw)
+            e = hipMemcpy(wbuf_tab, wbuf_ptrs.data(), nw * sizeof(uintptr_t),
+                          hipMemcpyHostToDevice);
+          if (e == hipSuccess) {
+            launch_multi_update((float*)w, (float* const*)g_tab,
+                                (float* const*)wbuf_tab, (float*)alpha_bar,
+                                gamma, inv_batch, inv_N, d, &a, vec4 ? 1 : 0,
+                                (hipStream_t)stream);
+            e = hipGetLastError();
+          }
+          if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+          (void)hipFree(tabs);
+          check(e, "multi_update");
+          return vec4;
         });
 
   register_libsvm(m);

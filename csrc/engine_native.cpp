@@ -31,7 +31,9 @@
 // Measured evolution on the flagship config (profiles/r02_wave_dispatch.md):
 // 39.9k updates/s (r01, per-round launches + events) -> 87.2k (batched
 // updates) -> 103k (event-free) -> 188k (wave dispatch, interleaved
-// mapping, wave-aware grid sizing). The RCCL multi-GPU server reuses this
+// mapping, wave-aware grid sizing) -> 370k (gradient kernel at 4 blocks
+// per CU instead of 1, row-bounded loads; profiles/r04_grad_occupancy.md).
+// The RCCL multi-GPU server reuses this
 // loop shape with peers instead of streams (csrc/server_dist.cpp).
 //
 // Synchronous mode (run_sync; asgd-sync, asaga-sync, sgd-mllib) is a
@@ -130,7 +132,7 @@ void launch_sgd_update_zero(float*, float*, float, float, int, hipStream_t);
 void launch_saga_update_zero(float*, float*, float*, float, float, float,
                              int, hipStream_t);
 void launch_multi_update(float*, float* const*, float* const*, float*, float,
-                         float, float, int, const MultiUpdateArgs*,
+                         float, float, int, const MultiUpdateArgs*, int,
                          hipStream_t);
 void launch_saga_commit_devn(float*, const int*, const float*, const int*,
                              int, hipStream_t);
@@ -597,6 +599,7 @@ struct NativeEngine {
   //    sequential application inside the kernel makes the result identical
   //    to launching the per-round update kernels back to back) ------------
   MultiUpdateArgs mu{};
+  bool mu_vec4 = false;  // float4 form: d % 4 == 0, 16-byte-aligned buffers
 
   void flush_batch(const std::vector<int>* snap_targets) {
     size_t si = 0;
@@ -611,7 +614,7 @@ struct NativeEngine {
       launch_multi_update((float*)w, (float* const*)g_tab_dev,
                           (float* const*)wbuf_tab_dev, (float*)alpha_bar,
                           (float)cfg.gamma, (float)inv_batch, (float)inv_N,
-                          cfg.d, &mu, sstream);
+                          cfg.d, &mu, mu_vec4 ? 1 : 0, sstream);
       HIP_CHECK(hipGetLastError());
       launched = true;
       mu.n = 0;
@@ -633,6 +636,14 @@ struct NativeEngine {
       const double gamma_k = cfg.gamma / std::sqrt((double)(k / cfg.P + 1));
       mu.scale[mu.n] = (float)(gamma_k * inv_batch);
     }
+    // multi_update_kernel reads every g of the batch before it zeroes any:
+    // a worker may appear only once per batch (it is redispatched, and can
+    // complete again, only after the flush)
+    for (int j = 0; j < mu.n; ++j)
+      if (mu.gw[j] == wid)
+        throw std::runtime_error(
+            "native engine: worker " + std::to_string(wid) +
+            " accepted twice in one update batch");
     mu.gw[mu.n] = wid;
     mu.n += 1;
     if (cfg.algo == 1) wk.pending_commit = true;
@@ -793,11 +804,14 @@ struct NativeEngine {
                                              hipStreamNonBlocking));
       wave_bper = query_grad_grid(wave_max_rows);
       if (!std::getenv("ASYNCAMD_GRAD_GRID")) {
-        // measured (flagship, P=32): with interleaved full-P waves the
-        // chip is best fed by ~512-768 TOTAL blocks, each carrying many
-        // sampled rows (deep pipelines) — per-worker grids sized as if
-        // launched alone left 5 rows/block and 114k updates/s vs 186k
-        // at 16-24 blocks/worker (same-box sweep, ASYNCAMD_GRAD_GRID)
+        // per-worker grids are sized for the WAVE (512 total blocks), not
+        // as if launched alone (that left 5 sampled rows per block at
+        // P=32). Re-measured with the gradient kernel at 4 blocks per CU
+        // (flagship, interleaved env-override A/B): 16 blocks/worker
+        // 354-370k updates/s, 24: 381-410k, 32: 402-420k, 48: 364-366k.
+        // 32 is faster but is NOT adopted: it moves the final weights
+        // further from the parent schedule's than the parent's own
+        // run-to-run distance (profiles/r04_grad_occupancy.md, section 4)
         wave_bper = std::min(wave_bper, std::max(8, 512 / cfg.P));
       }
       // interleaved block->slot mapping measured +21% on the flagship
@@ -810,9 +824,11 @@ struct NativeEngine {
     inv_N = 1.0 / (double)cfg.N;
     {  // device pointer tables for the batched update kernel
       std::vector<float*> hg(cfg.P), hw(cfg.P);
+      mu_vec4 = cfg.d % 4 == 0 && ((w | alpha_bar) & 15) == 0;
       for (int i = 0; i < cfg.P; ++i) {
         hg[i] = (float*)ws[i].g;
         hw[i] = (float*)ws[i].wbuf;
+        mu_vec4 = mu_vec4 && ((ws[i].g | ws[i].wbuf) & 15) == 0;
       }
       HIP_CHECK(hipMalloc(&g_tab_dev, cfg.P * sizeof(float*)));
       HIP_CHECK(hipMalloc(&wbuf_tab_dev, cfg.P * sizeof(float*)));

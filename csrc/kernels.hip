@@ -4,8 +4,9 @@
 //   K1 grad_dense      — fused Philox sample mask + per-row dot + scaled
 //                        accumulate (reference gradfun SparkASGDThread.scala:
 //                        423-438 + reducePartition fold RDD.scala:1103-1123);
-//                        three forms: grad_dense_pipe_kernel (LDS row queue
-//                        + depth-4 register pipeline), scan_rows_kernel +
+//                        three forms: grad_dense_pipe_kernel and its
+//                        whole-wave twin grad_dense_wave_kernel (LDS row
+//                        queue + register pipeline), scan_rows_kernel +
 //                        grad_dense_list_kernel (split form for the graph
 //                        engine's scan/compute overlap), and a generic
 //                        fallback for d > 2048 or d % 4 != 0.
@@ -23,14 +24,21 @@
 //    the dominant fixed cost per round (8.1M rows; 32-bit integer multiply
 //    is slow on the VALU), so each wave covers 256 rows per eval step.
 //  * row processing is latency-bound, not bandwidth-bound, at the
-//    reference's sampling rates (b=0.01 samples ~81k of 8.1M rows): rows are
-//    processed by SUB-WAVES of LPR lanes (template param 64/32/16), so a
-//    wave keeps 64/LPR rows in flight — raising memory-level parallelism
-//    without extra registers.
-//  * dense path: w staged in LDS; per-sub-wave fp32 gradient slabs in LDS
-//    (LDS = (1 + 4*64/LPR)*d*4 bytes); finalize writes per-block partials
-//    to a transposed slab, summed by reduce_partials (no global atomics:
-//    a d-wide atomicAdd finalize serialized on 784 addresses).
+//    reference's sampling rates (b=0.01 samples ~81k of 8.1M rows). The
+//    main dense path (grad_dense_pipe_body, d <= 2048, d % 4 == 0) hides
+//    the latency two ways: each wave keeps DEPTH whole rows in flight in a
+//    register pipeline of bounds-checked buffer loads, and several blocks
+//    share a CU — the body is force-inlined under a waves-per-SIMD launch
+//    bound chosen per shape (PipeShape) so the pipeline costs ~126 VGPRs
+//    at the flagship shape, not the whole register file.
+//  * dense path: w staged in LDS; one fp32 gradient slab per wave in LDS
+//    (LDS = 5 * ITERS*256 * 4 bytes + the row queue); the wave/flag
+//    launches finish with one atomicAdd per nonzero element per block into
+//    the worker's g, the graph engine's forms write per-block partials to
+//    a transposed slab summed by reduce_partials.
+//  * the generic fallback (grad_dense_kernel: d > 2048 or d % 4 != 0)
+//    processes rows by SUB-WAVES of LPR lanes (64/32/16) with per-sub-wave
+//    slabs (LDS = (1 + 4*64/LPR)*d*4 bytes).
 //  * sparse path: w stays in L2 (rcv1 d=47236 -> 189 KB; L2 is 4 MiB/XCD);
 //    gradient scatter via global fp32 atomics (~73 nnz/row, low contention).
 //  * bf16 rows load as ushort4 (8 B/lane) — scalar bf16 loads halve
@@ -40,6 +48,7 @@
 #include <hip/hip_bf16.h>
 #include <cstdint>
 #include <cstdlib>
+#include <type_traits>
 #include "philox.h"
 #include "grad_wave.h"
 
@@ -254,11 +263,13 @@ __global__ __launch_bounds__(BLOCK) void grad_dense_kernel(
 
 // ------------------------------------------------- K1 pipelined (queue)
 //
-// Two-phase dense gradient. Phase 1 (scan): Philox decides 4 rows per eval;
-// sampled rows are appended to an LDS queue TOGETHER with their y (and SAGA
-// alpha) values — prefetching them here keeps ordinary vmem loads out of
-// the pipelined phase (hipcc drains vmcnt(0) at any ordinary-load use,
-// CDNA guide §5.5 trap (b): measured one full drain per row from y[rr]).
+// Three-phase dense gradient. Phase 1 (scan): Philox decides 4 rows per
+// eval; sampled row ids are appended to an LDS queue (no global load in the
+// scan). Phase 1b (fetch): one strided pass loads y (and the SAGA alpha)
+// for the whole queue into LDS, all loads in flight at once — staging them
+// keeps ordinary vmem loads out of the pipelined phase (hipcc drains
+// vmcnt(0) at any ordinary-load use, CDNA guide §5.5 trap (b): measured one
+// full drain per row from y[rr]).
 // Phase 2 (process): waves drain the queue round-robin with a DEPTH-deep
 // statically-unrolled register pipeline; row loads are UNCONDITIONAL
 // bounds-checked buffer loads (per-row scalar descriptor) with a
@@ -267,6 +278,45 @@ __global__ __launch_bounds__(BLOCK) void grad_dense_kernel(
 // reuses the pipeline registers; X is read exactly once per sampled row.
 
 #define QCAP 2048
+
+// ---- pipelined-kernel shape selection: the ONE place that decides ITERS,
+// DEPTH and the occupancy hint. The launchers and the query_dense_kernel
+// binding both go through it.
+//
+// Occupancy hint = second argument of __launch_bounds__ = minimum waves per
+// SIMD; a 256-thread block is one wave per SIMD, so the hint is also the
+// number of blocks meant to share a CU. Without it (and with the body out
+// of line, as it once was) the compiler spent the whole register file:
+// 248 VGPR + 30 AGPR at the flagship shape, one block per CU. The hint is
+// the largest value at which
+//   * dynamic LDS still lets that many blocks share the CU's 160 KiB, and
+//   * the DEPTH x ITERS row buffers (2 VGPRs per bf16x4, 4 per f32x4) plus
+//     PIPE_WORK_VGPRS of working registers fit the per-wave budget
+//     (128 / 168 / 256 / 512 registers at 4 / 3 / 2 / 1 waves per SIMD),
+// so that no instantiation spills (checked with
+// -Rpass-analysis=kernel-resource-usage over every selectable shape).
+#define CU_LDS_BYTES 163840
+#define PIPE_WORK_VGPRS 76
+
+constexpr size_t pipe_lds_bytes(int iters, bool saga) {
+  return (size_t)(1 + 4) * (iters * 256) * sizeof(float) +
+         (size_t)QCAP * sizeof(float) * (saga ? 3 : 1) +
+         (QCAP + 1) * sizeof(int);
+}
+constexpr int occupancy_hint(size_t lds_bytes, int xt_bytes, int depth,
+                             int iters) {
+  const int need = depth * iters * (xt_bytes == 2 ? 2 : 4) + PIPE_WORK_VGPRS;
+  const int by_regs = need <= 128 ? 4 : need <= 168 ? 3 : need <= 256 ? 2 : 1;
+  const int by_lds = (int)(CU_LDS_BYTES / lds_bytes);
+  const int h = by_regs < by_lds ? by_regs : by_lds;
+  return h < 1 ? 1 : h;
+}
+template <typename XT, bool SAGA, int DEPTH, int ITERS>
+struct PipeShape {
+  static constexpr size_t LDS = pipe_lds_bytes(ITERS, SAGA);
+  static constexpr int HINT =
+      occupancy_hint(LDS, (int)sizeof(XT), DEPTH, ITERS);
+};
 
 // Row-fragment types for the pipelined loaders. Loads are compiler-visible
 // buffer intrinsics: with unconditional compile-time load counts and
@@ -321,16 +371,22 @@ __device__ __forceinline__ void cvt4(const B16x4& r, float o[4]) {
 }
 
 // Per-row buffer descriptor: base = row start (scalar via readfirstlane),
-// num_records = bytes to the end of X -> hardware bounds check returns 0 for
-// the padded over-read of the last row (w_lds is zero-padded, so padded
-// elements contribute nothing).
+// num_records = the row's OWN byte length (clamped to what remains of X) ->
+// the hardware bounds check zero-fills every lane past the row end and
+// fetches nothing for it. The pipelined loaders always issue ITERS*64 lanes
+// per row; with a descriptor reaching to the end of X the lanes past d were
+// real reads of the NEXT row (d=784: 480 of 2,048 B, +30% traffic), and
+// although w_lds is zero-padded a non-finite value there still poisoned the
+// dot product (0 * NaN). d % 4 == 0 keeps every lane's 4-element access
+// wholly inside or wholly outside the row.
 template <typename XT>
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t row_rsrc(
     const XT* X, long total_elems, int rr, int d) {
   const size_t off = (size_t)rr * d;
   const uint64_t rem_bytes = (uint64_t)(total_elems - off) * sizeof(XT);
-  const uint32_t nrec =
-      rem_bytes > 0xFFFFFFF0ull ? 0xFFFFFFF0u : (uint32_t)rem_bytes;
+  const uint64_t row_bytes = (uint64_t)d * sizeof(XT);
+  const uint32_t nrec = (uint32_t)(rem_bytes < row_bytes ? rem_bytes
+                                                         : row_bytes);
   return __builtin_amdgcn_make_buffer_rsrc((void*)(X + off), 0, nrec,
                                            0x00020000);
 }
@@ -513,8 +569,10 @@ __global__ __launch_bounds__(PBLOCK) void grad_dense_list_kernel(
   }
 }
 
+// __forceinline__ is load-bearing: left out of line, the body inherits no
+// launch bounds from its kernels and takes the whole register file.
 template <typename XT, bool SAGA, int PBLOCK, int DEPTH, int ITERS>
-__device__ void grad_dense_pipe_body(
+__device__ __forceinline__ void grad_dense_pipe_body(
     const XT* __restrict__ X, const float* __restrict__ y,
     const float* __restrict__ w, float* __restrict__ g_out,
     float* __restrict__ g_part, int* __restrict__ n_out,
@@ -556,7 +614,9 @@ __device__ void grad_dense_pipe_body(
   long gi = bid;
   bool done = false;
   while (!done) {
-    // ---- scan phase (also prefetches y / alpha into the queue)
+    // ---- scan phase: enqueues row ids only (a y[row] load per hit would
+    // expose one global-load latency per scan iteration ahead of the
+    // iteration's barrier)
     while (true) {
       __syncthreads();
       if (gi >= ngroups || *qn >= QCAP - RPB) break;
@@ -571,10 +631,7 @@ __device__ void grad_dense_pipe_body(
         for (int i = 0; i < 4; ++i) {
           if (4L * lane + i < rem && (take_all || xs[i] < threshold)) {
             const int pos = atomicAdd(qn, 1);
-            const int row = (int)(lrow + i);
-            rowq[pos] = row;
-            yq[pos] = y[row];
-            if (SAGA) aq[pos] = alpha[row];
+            rowq[pos] = (int)(lrow + i);
           }
         }
       }
@@ -582,6 +639,14 @@ __device__ void grad_dense_pipe_body(
     }
     __syncthreads();
     const int nq = min(*qn, QCAP);
+    // ---- fetch phase: y (and the SAGA history scalar) for the whole queue
+    // in one strided pass, all loads in flight at once
+    for (int pos = threadIdx.x; pos < nq; pos += PBLOCK) {
+      const int row = rowq[pos];
+      yq[pos] = y[row];
+      if (SAGA) aq[pos] = alpha[row];
+    }
+    __syncthreads();
     // ---- process phase: DEPTH-deep static pipeline, buffer loads only
     typename RV::T buf[DEPTH][ITERS];
     // the counted-wait protocol needs EXACTLY ITERS loads per slot: a
@@ -699,7 +764,9 @@ __device__ void grad_dense_pipe_body(
 }
 
 template <typename XT, bool SAGA, int PBLOCK, int DEPTH, int ITERS>
-__global__ __launch_bounds__(PBLOCK) void grad_dense_pipe_kernel(
+__global__
+__launch_bounds__(PBLOCK, (PipeShape<XT, SAGA, DEPTH, ITERS>::HINT))
+void grad_dense_pipe_kernel(
     const XT* __restrict__ X, const float* __restrict__ y,
     const float* __restrict__ w, float* __restrict__ g_out,
     float* __restrict__ g_part, int* __restrict__ n_out,
@@ -724,7 +791,9 @@ __global__ __launch_bounds__(PBLOCK) void grad_dense_pipe_kernel(
 // device table built once at engine init; the per-round variables (slot
 // list, Philox round keys, serials) travel by value in the launch args.
 template <typename XT, bool SAGA, int PBLOCK, int DEPTH, int ITERS>
-__global__ __launch_bounds__(PBLOCK) void grad_dense_wave_kernel(
+__global__
+__launch_bounds__(PBLOCK, (PipeShape<XT, SAGA, DEPTH, ITERS>::HINT))
+void grad_dense_wave_kernel(
     const GradWaveSlot* __restrict__ slots, GradWaveCmd cmd, int d,
     uint64_t seed, uint32_t threshold, int take_all, int objective) {
   const int si = cmd.interleave ? (int)(blockIdx.x % cmd.n)
@@ -1078,32 +1147,78 @@ __global__ void saga_commit_devn_kernel(float* __restrict__ alpha,
 // (<= 4 KB), so a batch costs exactly one launch and no H2D staging.
 #include "multi_update.h"
 
-__global__ __launch_bounds__(256) void multi_update_kernel(
+// The batch's gradients are FETCHED first, MU_CHUNK at a time (pointer from
+// g_tab, then g[i]; unconditional loads with a clamped index so all of a
+// chunk's loads are in flight together), then APPLIED to wi (and alpha_bar)
+// in the same j order with the same expressions as a plain sequential loop,
+// and only then are the consumed accumulators zeroed. A `g[i] = 0` store
+// interleaved with the loads would serialize them into a chain of 2n
+// dependent global loads. Deferring the zero stores is valid only because a
+// worker id appears AT MOST ONCE per batch (the engine redispatches a worker
+// only after the flush; checked on the host where the batch is assembled).
+// VEC4 (d % 4 == 0, 16-byte-aligned buffers) moves float4 per lane: d=784
+// is 196 lanes over 4 blocks of 64.
+#define MU_BLOCK 64
+#define MU_CHUNK 8
+
+__device__ __forceinline__ void mu_asgd(float& w, float g, float scale) {
+  w -= scale * g;
+}
+__device__ __forceinline__ void mu_saga(float& w, float& ab, float g,
+                                        float gamma, float inv_batch,
+                                        float inv_N) {
+  w -= gamma * (inv_batch * g + ab);
+  ab += inv_N * g;
+}
+
+template <bool VEC4>
+__global__ __launch_bounds__(MU_BLOCK) void multi_update_kernel(
     float* __restrict__ w, float* const* __restrict__ g_tab,
     float* const* __restrict__ wbuf_tab, float* __restrict__ alpha_bar,
     float gamma, float inv_batch, float inv_N, int d, MultiUpdateArgs a) {
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < d;
-       i += gridDim.x * blockDim.x) {
-    float wi = w[i];
-    if (a.algo == 0) {
-      for (int j = 0; j < a.n; ++j) {
-        float* g = g_tab[a.gw[j]];
-        wi -= a.scale[j] * g[i];
-        g[i] = 0.f;
+  using V = typename std::conditional<VEC4, float4, float>::type;
+  const int nel = VEC4 ? d >> 2 : d;
+  const V zero = V{};
+  for (int i = blockIdx.x * MU_BLOCK + threadIdx.x; i < nel;
+       i += gridDim.x * MU_BLOCK) {
+    V wi = reinterpret_cast<const V*>(w)[i];
+    V ab = zero;
+    if (a.algo != 0) ab = reinterpret_cast<const V*>(alpha_bar)[i];
+    for (int j0 = 0; j0 < a.n; j0 += MU_CHUNK) {
+      V gv[MU_CHUNK];
+#pragma unroll
+      for (int c = 0; c < MU_CHUNK; ++c) {
+        const int j = min(j0 + c, a.n - 1);
+        gv[c] = reinterpret_cast<const V*>(g_tab[a.gw[j]])[i];
       }
-    } else {
-      float ab = alpha_bar[i];
-      for (int j = 0; j < a.n; ++j) {
-        float* g = g_tab[a.gw[j]];
-        const float gi = g[i];
-        wi -= gamma * (inv_batch * gi + ab);
-        ab += inv_N * gi;
-        g[i] = 0.f;
+#pragma unroll
+      for (int c = 0; c < MU_CHUNK; ++c) {
+        const int j = j0 + c;
+        if (j < a.n) {
+          if constexpr (VEC4) {
+            if (a.algo == 0) {
+              const float sc = a.scale[j];
+              mu_asgd(wi.x, gv[c].x, sc); mu_asgd(wi.y, gv[c].y, sc);
+              mu_asgd(wi.z, gv[c].z, sc); mu_asgd(wi.w, gv[c].w, sc);
+            } else {
+              mu_saga(wi.x, ab.x, gv[c].x, gamma, inv_batch, inv_N);
+              mu_saga(wi.y, ab.y, gv[c].y, gamma, inv_batch, inv_N);
+              mu_saga(wi.z, ab.z, gv[c].z, gamma, inv_batch, inv_N);
+              mu_saga(wi.w, ab.w, gv[c].w, gamma, inv_batch, inv_N);
+            }
+          } else {
+            if (a.algo == 0) mu_asgd(wi, gv[c], a.scale[j]);
+            else mu_saga(wi, ab, gv[c], gamma, inv_batch, inv_N);
+          }
+        }
       }
-      alpha_bar[i] = ab;
     }
-    w[i] = wi;
-    for (int j = 0; j < a.m; ++j) wbuf_tab[a.sw[j]][i] = wi;
+    for (int j = 0; j < a.n; ++j)
+      reinterpret_cast<V*>(g_tab[a.gw[j]])[i] = zero;
+    if (a.algo != 0) reinterpret_cast<V*>(alpha_bar)[i] = ab;
+    reinterpret_cast<V*>(w)[i] = wi;
+    for (int j = 0; j < a.m; ++j)
+      reinterpret_cast<V*>(wbuf_tab[a.sw[j]])[i] = wi;
   }
 }
 
@@ -1312,6 +1427,46 @@ static inline int pick_lpr(int d) {
   return 64;
 }
 
+// Pipelined-kernel template parameters for a feature dim (callers guarantee
+// d % 4 == 0 and d <= 2048). Depth: measured on the wave kernel, 6 wins at
+// ITERS <= 4 and 4 at the wider fp32 shapes (profiles/r04_grad_occupancy.md);
+// solo launches keep 4. ASYNCAMD_PIPE_DEPTH overrides (1, 2, 4, 6 or 8; any
+// other value runs as 4).
+static inline int pipe_iters(int d) {
+  const int it = (d + 255) / 256;
+  return it < 1 ? 1 : (it > 8 ? 8 : it);
+}
+static inline int pipe_depth(int iters, bool wave) {
+  const char* dps = std::getenv("ASYNCAMD_PIPE_DEPTH");  // re-read: sweeps
+  const int depth = dps ? std::atoi(dps) : (wave && iters <= 4 ? 6 : 4);
+  return (depth == 1 || depth == 2 || depth == 6 || depth == 8) ? depth : 4;
+}
+
+// Calls f(integral_constant<ITERS>, integral_constant<DEPTH>) for the
+// runtime (iters, depth) pair: the one switch over the instantiated shapes.
+template <typename F>
+static void with_pipe_shape(int iters, int depth, F&& f) {
+  auto with_depth = [&](auto IT) {
+    switch (depth) {
+      case 1: f(IT, std::integral_constant<int, 1>{}); break;
+      case 2: f(IT, std::integral_constant<int, 2>{}); break;
+      case 6: f(IT, std::integral_constant<int, 6>{}); break;
+      case 8: f(IT, std::integral_constant<int, 8>{}); break;
+      default: f(IT, std::integral_constant<int, 4>{}); break;
+    }
+  };
+  switch (iters) {
+    case 1: with_depth(std::integral_constant<int, 1>{}); break;
+    case 2: with_depth(std::integral_constant<int, 2>{}); break;
+    case 3: with_depth(std::integral_constant<int, 3>{}); break;
+    case 4: with_depth(std::integral_constant<int, 4>{}); break;
+    case 5: with_depth(std::integral_constant<int, 5>{}); break;
+    case 6: with_depth(std::integral_constant<int, 6>{}); break;
+    case 7: with_depth(std::integral_constant<int, 7>{}); break;
+    default: with_depth(std::integral_constant<int, 8>{}); break;
+  }
+}
+
 template <typename XT, bool SAGA>
 static void launch_dense(const XT* X, const float* y, const float* w,
                          float* g_out, float* g_part, int* n_out,
@@ -1329,39 +1484,17 @@ static void launch_dense(const XT* X, const float* y, const float* w,
   const char* np = std::getenv("ASYNCAMD_NO_PIPE");
   const bool pipe_ok = (d % 4 == 0) && (d <= 2048) && !(np && np[0] == '1');
   if (pipe_ok) {
-    const int iters = (d + 255) / 256;
-    const size_t smem = (size_t)(1 + 4) * (iters * 256) * sizeof(float) +
-                        (size_t)QCAP * sizeof(float) * (SAGA ? 3 : 1) +
-                        (QCAP + 1) * sizeof(int);
-    const char* dps = std::getenv("ASYNCAMD_PIPE_DEPTH");
-    const int depth = dps ? std::atoi(dps) : 4;
-#define LAUNCH_PIPE_D(IT, DP)                                                \
-    hipLaunchKernelGGL((grad_dense_pipe_kernel<XT, SAGA, 256, DP, IT>),      \
-                       dim3(grid), dim3(256), smem, stream, X, y, w, g_out,  \
-                       g_part, n_out, alpha, idx_out, e_out, pos_ctr,        \
-                       k_dev, commit_now, n_rows, d, seed, round_k,          \
-                       row_start, thr, take_all, objective, done_flag,       \
-                       done_val, done_arr)
-#define LAUNCH_PIPE(IT)                                                      \
-    do {                                                                     \
-      if (depth == 1) LAUNCH_PIPE_D(IT, 1);                                  \
-      else if (depth == 2) LAUNCH_PIPE_D(IT, 2);                             \
-      else if (depth == 6) LAUNCH_PIPE_D(IT, 6);                             \
-      else if (depth == 8) LAUNCH_PIPE_D(IT, 8);                             \
-      else LAUNCH_PIPE_D(IT, 4);                                             \
-    } while (0)
-    switch (iters) {
-      case 1: LAUNCH_PIPE(1); break;
-      case 2: LAUNCH_PIPE(2); break;
-      case 3: LAUNCH_PIPE(3); break;
-      case 4: LAUNCH_PIPE(4); break;
-      case 5: LAUNCH_PIPE(5); break;
-      case 6: LAUNCH_PIPE(6); break;
-      case 7: LAUNCH_PIPE(7); break;
-      default: LAUNCH_PIPE(8); break;
-    }
-#undef LAUNCH_PIPE
-#undef LAUNCH_PIPE_D
+    with_pipe_shape(pipe_iters(d), pipe_depth(pipe_iters(d), false),
+                    [&](auto IT, auto DP) {
+      constexpr int it = decltype(IT)::value, dp = decltype(DP)::value;
+      hipLaunchKernelGGL((grad_dense_pipe_kernel<XT, SAGA, 256, dp, it>),
+                         dim3(grid), dim3(256),
+                         (PipeShape<XT, SAGA, dp, it>::LDS), stream, X, y, w,
+                         g_out, g_part, n_out, alpha, idx_out, e_out,
+                         pos_ctr, k_dev, commit_now, n_rows, d, seed,
+                         round_k, row_start, thr, take_all, objective,
+                         done_flag, done_val, done_arr);
+    });
     return;
   }
   const int lpr = pick_lpr(d);
@@ -1505,53 +1638,69 @@ void launch_grad_dense_wave(const void* slots_dev, const void* cmd_host,
   const uint32_t thr = philox_threshold(rate);
   const int take_all = rate >= 1.0;
   const int grid = cmd->n * cmd->bper;
-  const int iters = (d + 255) / 256;
-  const size_t smem = (size_t)(1 + 4) * (iters * 256) * sizeof(float) +
-                      (size_t)QCAP * sizeof(float) * (saga ? 3 : 1) +
-                      (QCAP + 1) * sizeof(int);
-  const char* dps = std::getenv("ASYNCAMD_PIPE_DEPTH");
-  // wave-measured: depth 6 wins at small ITERS (d<=1024, flagship +8%);
-  // keep 4 at larger feature dims where the deeper pipeline's register
-  // pressure bites (epsilon d=2000). Solo kernels keep 4 everywhere.
-  const int depth = dps ? std::atoi(dps) : (iters <= 4 ? 6 : 4);
+  const int iters = pipe_iters(d);
   (void)max_rows;
-#define WAVE_LAUNCH_D(XT, SG, IT, DP)                                        \
-  hipLaunchKernelGGL((grad_dense_wave_kernel<XT, SG, 256, DP, IT>),          \
-                     dim3(grid), dim3(256), smem, stream,                    \
-                     (const GradWaveSlot*)slots_dev, *cmd, d, seed, thr,     \
-                     take_all, objective)
-#define WAVE_LAUNCH(XT, SG, IT)                                              \
-  do {                                                                       \
-    if (depth == 1) WAVE_LAUNCH_D(XT, SG, IT, 1);                            \
-    else if (depth == 2) WAVE_LAUNCH_D(XT, SG, IT, 2);                       \
-    else if (depth == 6) WAVE_LAUNCH_D(XT, SG, IT, 6);                       \
-    else if (depth == 8) WAVE_LAUNCH_D(XT, SG, IT, 8);                       \
-    else WAVE_LAUNCH_D(XT, SG, IT, 4);                                       \
-  } while (0)
-#define WAVE_ITERS(XT, SG)                                                   \
-  do {                                                                       \
-    switch (iters) {                                                         \
-      case 1: WAVE_LAUNCH(XT, SG, 1); break;                                 \
-      case 2: WAVE_LAUNCH(XT, SG, 2); break;                                 \
-      case 3: WAVE_LAUNCH(XT, SG, 3); break;                                 \
-      case 4: WAVE_LAUNCH(XT, SG, 4); break;                                 \
-      case 5: WAVE_LAUNCH(XT, SG, 5); break;                                 \
-      case 6: WAVE_LAUNCH(XT, SG, 6); break;                                 \
-      case 7: WAVE_LAUNCH(XT, SG, 7); break;                                 \
-      default: WAVE_LAUNCH(XT, SG, 8); break;                                \
-    }                                                                        \
-  } while (0)
-#define WAVE_DISPATCH(XT)                                                    \
-  do {                                                                       \
-    if (saga) WAVE_ITERS(XT, true);                                          \
-    else WAVE_ITERS(XT, false);                                              \
-  } while (0)
-  if (x_is_bf16) WAVE_DISPATCH(__hip_bfloat16);
-  else WAVE_DISPATCH(float);
-#undef WAVE_DISPATCH
-#undef WAVE_ITERS
-#undef WAVE_LAUNCH
-#undef WAVE_LAUNCH_D
+  auto go = [&](auto xt, auto sg) {
+    using XT = decltype(xt);
+    constexpr bool SG = decltype(sg)::value;
+    with_pipe_shape(iters, pipe_depth(iters, true), [&](auto IT, auto DP) {
+      constexpr int it = decltype(IT)::value, dp = decltype(DP)::value;
+      hipLaunchKernelGGL((grad_dense_wave_kernel<XT, SG, 256, dp, it>),
+                         dim3(grid), dim3(256),
+                         (PipeShape<XT, SG, dp, it>::LDS), stream,
+                         (const GradWaveSlot*)slots_dev, *cmd, d, seed, thr,
+                         take_all, objective);
+    });
+  };
+  if (x_is_bf16) {
+    if (saga) go(__hip_bfloat16{}, std::true_type{});
+    else go(__hip_bfloat16{}, std::false_type{});
+  } else {
+    if (saga) go(float{}, std::true_type{});
+    else go(float{}, std::false_type{});
+  }
+}
+
+// What a dense gradient launch at feature dim d will run: fills
+// out = {iters, depth, occupancy hint, numRegs, localSizeBytes (scratch),
+// dynamic LDS bytes, max active 256-thread blocks per CU with that LDS, 0}.
+// wave = 1 describes grad_dense_wave_kernel, 0 the solo
+// grad_dense_pipe_kernel. Returns 0, a hipError_t, or -1 when d is not
+// served by the pipelined kernels.
+int query_dense_kernel(int d, int x_is_bf16, int saga, int wave, int* out) {
+  if (d <= 0 || d % 4 != 0 || d > 2048) return -1;
+  const int iters = pipe_iters(d);
+  int rc = 0;
+  auto go = [&](auto xt, auto sg) {
+    using XT = decltype(xt);
+    constexpr bool SG = decltype(sg)::value;
+    with_pipe_shape(iters, pipe_depth(iters, wave != 0),
+                    [&](auto IT, auto DP) {
+      constexpr int it = decltype(IT)::value, dp = decltype(DP)::value;
+      using Shape = PipeShape<XT, SG, dp, it>;
+      const void* fn =
+          wave ? (const void*)grad_dense_wave_kernel<XT, SG, 256, dp, it>
+               : (const void*)grad_dense_pipe_kernel<XT, SG, 256, dp, it>;
+      hipFuncAttributes attr;
+      hipError_t e = hipFuncGetAttributes(&attr, fn);
+      int nb = 0;
+      if (e == hipSuccess)
+        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, 256,
+                                                         Shape::LDS);
+      if (e != hipSuccess) { rc = (int)e; return; }
+      out[0] = it; out[1] = dp; out[2] = Shape::HINT;
+      out[3] = attr.numRegs; out[4] = (int)attr.localSizeBytes;
+      out[5] = (int)Shape::LDS; out[6] = nb; out[7] = 0;
+    });
+  };
+  if (x_is_bf16) {
+    if (saga) go(__hip_bfloat16{}, std::true_type{});
+    else go(__hip_bfloat16{}, std::false_type{});
+  } else {
+    if (saga) go(float{}, std::true_type{});
+    else go(float{}, std::false_type{});
+  }
+  return rc;
 }
 
 void launch_scan_rows_wave(const void* slots_dev, const void* cmd_host,
@@ -1815,15 +1964,25 @@ void launch_saga_update_fused(float* w, float* g, float* alpha_bar,
                      d);
 }
 
+// ``vec4`` selects the float4 form (caller guarantees d % 4 == 0 and
+// 16-byte-aligned w / alpha_bar / g / wbuf buffers).
 void launch_multi_update(float* w, float* const* g_tab,
                          float* const* wbuf_tab, float* alpha_bar,
                          float gamma, float inv_batch, float inv_N, int d,
-                         const MultiUpdateArgs* a, hipStream_t stream) {
-  int grid = (d + 255) / 256;
-  if (grid > 1024) grid = 1024;
-  hipLaunchKernelGGL(multi_update_kernel, dim3(grid), dim3(256), 0, stream,
-                     w, g_tab, wbuf_tab, alpha_bar, gamma, inv_batch, inv_N,
-                     d, *a);
+                         const MultiUpdateArgs* a, int vec4,
+                         hipStream_t stream) {
+  const int nel = vec4 ? d / 4 : d;
+  int grid = (nel + MU_BLOCK - 1) / MU_BLOCK;
+  if (grid > 4096) grid = 4096;
+  if (grid < 1) grid = 1;
+  if (vec4)
+    hipLaunchKernelGGL(multi_update_kernel<true>, dim3(grid), dim3(MU_BLOCK),
+                       0, stream, w, g_tab, wbuf_tab, alpha_bar, gamma,
+                       inv_batch, inv_N, d, *a);
+  else
+    hipLaunchKernelGGL(multi_update_kernel<false>, dim3(grid),
+                       dim3(MU_BLOCK), 0, stream, w, g_tab, wbuf_tab,
+                       alpha_bar, gamma, inv_batch, inv_N, d, *a);
 }
 
 // One barrier round of the native engine's synchronous mode. The work is
