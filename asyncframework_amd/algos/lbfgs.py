@@ -21,7 +21,8 @@ import torch
 
 
 def _loss_grad(X: torch.Tensor, y: torch.Tensor, w: torch.Tensor,
-               objective: str) -> Tuple[float, torch.Tensor]:
+               objective: str, l2: float = 0.0
+               ) -> Tuple[float, torch.Tensor]:
     Xf = X if X.dtype == torch.float32 else X.float()
     z = Xf @ w
     if objective == "logistic":
@@ -33,6 +34,13 @@ def _loss_grad(X: torch.Tensor, y: torch.Tensor, w: torch.Tensor,
         r = z - y
         loss = (r * r).mean()
         g = 2.0 * (Xf.t() @ r) / X.shape[0]
+    if l2 != 0.0:
+        # c*(l2/2)*||w||^2 with c = 2 for lsq (this loss is mean r^2, twice
+        # the (1/2)r^2 loss the SGD kernels step on), 1 for logistic: the
+        # same constant multiple of F the objective sweep reports
+        c = 1.0 if objective == "logistic" else 2.0
+        loss = loss + c * 0.5 * l2 * w.dot(w)
+        g = g + c * l2 * w
     return float(loss), g
 
 
@@ -46,7 +54,10 @@ class LBFGS:
 
     def __init__(self, memory: int = 10, max_iter: int = 100,
                  tol: float = 1e-8, printer_freq: int = 100,
-                 objective: str = "lsq"):
+                 objective: str = "lsq", l2: float = 0.0):
+        if not (l2 >= 0.0 and l2 < float("inf")):
+            raise ValueError(f"l2 must be finite and non-negative, got {l2!r}")
+        self.l2 = float(l2)
         self.m = memory
         self.max_iter = max_iter
         self.tol = tol
@@ -66,7 +77,7 @@ class LBFGS:
         self._hist = [(0, w.detach().cpu().clone())]
         S: List[torch.Tensor] = []
         Y: List[torch.Tensor] = []
-        loss, g = _loss_grad(X, y, w, self.objective)
+        loss, g = _loss_grad(X, y, w, self.objective, self.l2)
         for it in range(self.max_iter):
             if float(g.norm()) < self.tol:
                 break
@@ -95,7 +106,7 @@ class LBFGS:
                 gTp = -float(g.dot(g))
             while step > 1e-12:
                 new_loss, new_g = _loss_grad(X, y, w + step * p,
-                                             self.objective)
+                                             self.objective, self.l2)
                 if new_loss <= loss + c1 * step * gTp:
                     break
                 step *= 0.5

@@ -27,7 +27,7 @@ import argparse
 import sys
 from typing import List, Optional
 
-from ..engine.config import EngineConfig
+from ..engine.config import EngineConfig, check_penalties
 from ..utils import logfmt
 from .. import run as runner
 
@@ -66,6 +66,12 @@ def _engine_flags(p: argparse.ArgumentParser) -> None:
                    help="periodic optimizer-state snapshot file")
     p.add_argument("--checkpoint-every", type=int, default=0,
                    help="checkpoint every N applied updates (0 = off)")
+    p.add_argument("--l2", type=float, default=0.0,
+                   help="L2 penalty (l2/2)*||w||^2, applied as weight decay "
+                        "in the update step (default 0)")
+    p.add_argument("--l1", type=float, default=0.0,
+                   help="L1 penalty l1*||w||_1, applied as a soft-threshold "
+                        "after the step (default 0)")
     p.add_argument("--resume-from", default="",
                    help="restore optimizer state from a checkpoint file "
                         "before running")
@@ -92,6 +98,7 @@ def _parse8(argv: List[str], prog: str):
 
 
 def _cfg13(a, algo: str, sync: bool) -> EngineConfig:
+    check_penalties(a.l2, a.l1)
     return EngineConfig(
         d=int(a.d), N=int(a.N), num_workers=int(a.numPart),
         num_iterations=int(a.numIter), gamma=float(a.gamma),
@@ -102,7 +109,7 @@ def _cfg13(a, algo: str, sync: bool) -> EngineConfig:
         history_placement=a.history_placement,
         worker_timeout_s=a.worker_timeout_s,
         checkpoint_path=a.checkpoint_path,
-        checkpoint_every=a.checkpoint_every)
+        checkpoint_every=a.checkpoint_every, l2=a.l2, l1=a.l1)
 
 
 def _run(cfg: EngineConfig, a, app: str, names, vals) -> None:
@@ -239,12 +246,13 @@ def sgd_mllib(argv: Optional[List[str]] = None) -> None:
     GradientDescent.runMiniBatchSGD with the 100-iteration weight-history
     hook, GradientDescent.scala:255-260)."""
     a = _parse8(argv if argv is not None else sys.argv[1:], "sgd-mllib")
+    check_penalties(a.l2, a.l1)
     cfg = EngineConfig(
         d=int(a.d), N=int(a.N), num_workers=int(a.numPart),
         num_iterations=int(a.numIter), gamma=float(a.gamma),
         batch_rate=float(a.b), algo="mllib", sync=True, printer_freq=100,
         objective=a.objective, dtype=a.dtype, device=a.device, seed=42,
-        delay_coeff=0.0)
+        delay_coeff=0.0, l2=a.l2, l1=a.l1)
     import os
     vals = [a.pathname, a.fname, a.d, a.N, a.numPart, a.numIter, a.gamma,
             a.b]

@@ -85,6 +85,16 @@ def restore(server: Server, workers: Optional[List[Worker]], state: Dict
             f"with num_workers={server.cfg.num_workers}")
     if state.get("cfg", {}).get("d") not in (None, server.cfg.d):
         raise ValueError("checkpoint dimensionality mismatch")
+    # a checkpoint from before the penalties existed has neither key: 0.0
+    for name in ("l2", "l1"):
+        ck_v = float(state.get("cfg", {}).get(name, 0.0))
+        now_v = float(getattr(server.cfg, name, 0.0))
+        if ck_v != now_v:
+            import warnings
+            warnings.warn(
+                f"checkpoint was taken with {name}={ck_v}, resuming with "
+                f"{name}={now_v}: the run continues on a different objective",
+                RuntimeWarning, stacklevel=2)
     server.k = int(state["k"])
     server.AC.setCurrentTime(int(state["current_time"]))
     server.w.copy_(state["w"].to(server.w.device))

@@ -3,6 +3,7 @@ MI355X engine flags."""
 
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass
 
 import torch
@@ -13,6 +14,24 @@ _DTYPES = {
     "bf16": torch.bfloat16,
     "fp16": torch.float16,
 }
+
+
+def check_penalties(l2: float, l1: float) -> None:
+    """Reject a negative or non-finite elastic-net coefficient."""
+    for name, v in (("l2", l2), ("l1", l1)):
+        v = float(v)
+        if not math.isfinite(v) or v < 0.0:
+            raise ValueError(
+                f"{name} must be a finite non-negative number, got {v!r}")
+
+
+def refuse_penalties(cfg, engine: str) -> None:
+    """Engines whose own update kernels carry no penalty term call this
+    first: a non-zero l1/l2 is refused by name, never silently ignored."""
+    assert not (getattr(cfg, "l1", 0.0) or getattr(cfg, "l2", 0.0)), (
+        f"{engine} does not support l1/l2 regularisation (its update "
+        f"kernels have no penalty term); use the native engine, the threads "
+        f"engine (AsyncEngine/SyncEngine) or the Python dist engine")
 
 
 @dataclass
@@ -44,6 +63,8 @@ class EngineConfig:
     worker_timeout_s: float = 0.0   # busy-worker timeout -> declared dead
                                     # (reference has none: a lost task left a
                                     # worker busy forever)
+    l2: float = 0.0                 # lambda_2: (l2/2)*||w||^2, gradient step
+    l1: float = 0.0                 # lambda_1: l1*||w||_1, prox (soft-threshold)
 
     def torch_dtype(self) -> torch.dtype:
         return _DTYPES[self.dtype]

@@ -27,7 +27,7 @@ import torch
 import torch.distributed as dist
 
 from ..data.shard import row_shards
-from .config import EngineConfig
+from .config import EngineConfig, refuse_penalties
 from .dist import DistEngine, _send
 from .local import RunResult
 from .messages import HDR, Dispatch, pack_dispatch
@@ -67,6 +67,7 @@ class NativeDistEngine:
 
     def __init__(self, cfg: EngineConfig, local_workers, device: torch.device,
                  mark_at: Optional[List[int]] = None):
+        refuse_penalties(cfg, "NativeDistEngine")
         assert not cfg.sync, "native dist server is async-only"
         # reuse DistEngine's group construction (same deterministic order +
         # eager communicator warm-up on every rank)

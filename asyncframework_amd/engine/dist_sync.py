@@ -24,7 +24,7 @@ from typing import List, Optional
 import torch
 import torch.distributed as dist
 
-from .config import EngineConfig
+from .config import EngineConfig, check_penalties
 from .local import RunResult
 from .messages import Dispatch
 from .worker import Worker
@@ -36,6 +36,7 @@ class AllReduceSyncEngine:
     def __init__(self, cfg: EngineConfig, local_workers: List[Worker],
                  device: torch.device):
         assert dist.is_initialized()
+        check_penalties(cfg.l2, cfg.l1)
         self.cfg = cfg
         self.workers = local_workers
         self.device = device
@@ -73,7 +74,15 @@ class AllReduceSyncEngine:
             dist.all_reduce(meta)
             total_rows = max(int(meta.item()), 1)
             gamma_k = cfg.gamma / math.sqrt(k + 1)
-            if cfg.algo == "mllib":
+            if cfg.l2 or cfg.l1:
+                # penalised step (every rank applies the same one): the
+                # update op carries the decay + soft-threshold
+                from .. import ops
+                ops.sgd_update(w, acc, gamma_k,
+                               1.0 / total_rows if cfg.algo == "mllib"
+                               else 1.0 / (cfg.batch_rate * cfg.N),
+                               l2=cfg.l2, l1=cfg.l1)
+            elif cfg.algo == "mllib":
                 # grad sum / ACTUAL minibatch size, SimpleUpdater step
                 # (reference GradientDescent.scala:287-290)
                 w.add_(acc, alpha=-gamma_k / total_rows)

@@ -34,7 +34,7 @@ from typing import List, Optional, Tuple
 
 import torch
 
-from .config import EngineConfig
+from .config import EngineConfig, refuse_penalties
 from .worker import Shard
 
 
@@ -46,6 +46,7 @@ class GraphEngine:
     def __init__(self, cfg: EngineConfig, shard: Shard,
                  device: torch.device, unroll: Optional[int] = None):
         # config-compat asserts first (testable without a GPU)
+        refuse_penalties(cfg, "GraphEngine")
         assert not (cfg.algo == "asaga"
                     and cfg.history_placement == "host"), \
             "host-spill history needs the threads engine"

@@ -384,21 +384,25 @@ class SyncEngine:
             if cfg.algo == "asaga":
                 # SparkASAGASync.scala:300-304: parRecs = b*N
                 ops.saga_update(srv.w, acc, srv.alpha_bar, cfg.gamma,
-                                1.0 / (cfg.batch_rate * cfg.N), 1.0 / cfg.N)
+                                1.0 / (cfg.batch_rate * cfg.N), 1.0 / cfg.N,
+                                l2=cfg.l2, l1=cfg.l1)
             elif cfg.algo == "mllib":
                 # MLlib GradientDescent.runMiniBatchSGD semantics: the
                 # gradient sum is divided by the ACTUAL minibatch size and
                 # stepped with stepSize/sqrt(iter), iter from 1 (reference
                 # mllib/.../optimization/GradientDescent.scala:287-290,
-                # SimpleUpdater).
+                # SimpleUpdater; l2 alone is SquaredL2Updater, l1 alone
+                # L1Updater — Updater.scala).
                 gamma_k = cfg.gamma / math.sqrt(k + 1)
                 ops.sgd_update(srv.w, acc, gamma_k,
-                               1.0 / max(nrows_round, 1))
+                               1.0 / max(nrows_round, 1), l2=cfg.l2,
+                               l1=cfg.l1)
             else:
                 # SparkASGDSync.scala:273-277
                 gamma_k = cfg.gamma / math.sqrt(k + 1)
                 ops.sgd_update(srv.w, acc, gamma_k,
-                               1.0 / (cfg.batch_rate * cfg.N))
+                               1.0 / (cfg.batch_rate * cfg.N), l2=cfg.l2,
+                               l1=cfg.l1)
             if k % cfg.printer_freq == 0:
                 if self.verbose:
                     print(f"Iteration {k} is finished")

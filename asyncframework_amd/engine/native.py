@@ -24,7 +24,7 @@ from typing import Dict, List, Optional, Tuple
 
 import torch
 
-from .config import EngineConfig
+from .config import EngineConfig, check_penalties
 from .worker import Shard
 
 _OBJ = {"lsq": 0, "logistic": 1}
@@ -36,6 +36,7 @@ class NativeLocalEngine:
     def __init__(self, cfg: EngineConfig, shards: List[Shard],
                  device: torch.device):
         # configuration errors first: nothing is imported or allocated yet
+        check_penalties(cfg.l2, cfg.l1)
         if cfg.sync:
             assert cfg.algo in _SYNC_MODE, (
                 f"native sync engine: unknown algo {cfg.algo!r}")
@@ -136,7 +137,8 @@ class NativeLocalEngine:
                     mark_lo=mark_lo, mark_hi=mark_hi,
                     max_wall_s=max_wall_s, snap_every=snapshot_every,
                     snap_ring=snap_ring.data_ptr() if snap_ring is not None
-                    else 0, snap_cap=snap_cap)
+                    else 0, snap_cap=snap_cap, l2=float(cfg.l2),
+                    l1=float(cfg.l1))
         torch.cuda.synchronize()
         if cfg.sync:
             res = self._core.native_sync_run(conf, self._bufs,

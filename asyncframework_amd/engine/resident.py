@@ -17,7 +17,7 @@ from typing import Dict, List, Optional, Tuple
 
 import torch
 
-from .config import EngineConfig
+from .config import EngineConfig, refuse_penalties
 from .worker import Shard
 
 _OBJ = {"lsq": 0, "logistic": 1}
@@ -27,6 +27,7 @@ _ALGO = {"asgd": 0, "asaga": 1}
 class ResidentEngine:
     def __init__(self, cfg: EngineConfig, shards: List[Shard],
                  device: torch.device, blocks_per_worker: int = 0):
+        refuse_penalties(cfg, "ResidentEngine")
         from .. import _hip_core
         self._core = _hip_core
         assert device.type == "cuda", "resident engine is GPU-only"

@@ -18,13 +18,14 @@ import torch
 
 from .. import ops
 from ..core.context import ASYNCcontext, RDDPartialRes, workerState
-from .config import EngineConfig
+from .config import EngineConfig, check_penalties
 from .messages import WorkerResult
 
 
 class Server:
     def __init__(self, cfg: EngineConfig, w0: Optional[torch.Tensor] = None,
                  device: Optional[torch.device] = None):
+        check_penalties(cfg.l2, cfg.l1)
         self.cfg = cfg
         self.device = device or torch.device(cfg.device)
         self.w = (w0.clone().float().to(self.device) if w0 is not None
@@ -81,19 +82,23 @@ class Server:
     def apply(self, res: WorkerResult) -> None:
         """Apply one accepted gradient. ASGD: g/parRecs, step
         gamma/sqrt(k/P+1) (SparkASGDThread.scala:188-192). ASAGA: SAGA
-        triple-axpy with constant step (SparkASAGAThread.scala:217-220)."""
+        triple-axpy with constant step (SparkASAGAThread.scala:217-220).
+        cfg.l2/cfg.l1 add weight decay and a soft-threshold to the same
+        step (eta = the step size used here)."""
         cfg = self.cfg
         g = res.g
         if g.device != self.device:
             g = g.to(self.device)
         if cfg.algo == "asaga":
             ops.saga_update(self.w, g, self.alpha_bar, cfg.gamma,
-                            1.0 / cfg.par_recs, 1.0 / cfg.N)
+                            1.0 / cfg.par_recs, 1.0 / cfg.N, l2=cfg.l2,
+                            l1=cfg.l1)
         else:
             # NB: k/numPart is Scala Int division in the reference
             # (SparkASGDThread.scala:190) — keep the integer semantics.
             gamma_k = cfg.gamma / math.sqrt(self.k // cfg.num_workers + 1)
-            ops.sgd_update(self.w, g, gamma_k, 1.0 / cfg.par_recs)
+            ops.sgd_update(self.w, g, gamma_k, 1.0 / cfg.par_recs,
+                           l2=cfg.l2, l1=cfg.l1)
 
     def maybe_log(self) -> Optional[int]:
         """printer_freq hook: returns current k if it logged

@@ -186,37 +186,44 @@ def spill_refresh(alpha_dev, alpha_pinned, y, rowlist, ylist, cnt, cap, *,
 
 
 def sgd_update(w: torch.Tensor, g: torch.Tensor, gamma_k: float,
-               inv_batch: float) -> None:
-    """Fused weight update (kernel K5)."""
+               inv_batch: float, *, l2: float = 0.0, l1: float = 0.0) -> None:
+    """Fused weight update (kernel K5). Non-zero l2/l1: weight decay and
+    soft-threshold in the same kernel (docs/KERNELS.md, Updates)."""
     if w.is_cuda:
         mod = _require_hip("sgd_update")
         if mod is not None:
-            mod.sgd_update(w, g, float(gamma_k), float(inv_batch))
+            mod.sgd_update(w, g, float(gamma_k), float(inv_batch),
+                           float(l2), float(l1))
             return
-    torch_ref.sgd_update(w, g, gamma_k, inv_batch)
+    torch_ref.sgd_update(w, g, gamma_k, inv_batch, l2=l2, l1=l1)
 
 
 def saga_update(w: torch.Tensor, g: torch.Tensor, alpha_bar: torch.Tensor,
-                gamma: float, inv_batch: float, inv_N: float) -> None:
-    """Fused SAGA triple-axpy update (kernel K6)."""
+                gamma: float, inv_batch: float, inv_N: float, *,
+                l2: float = 0.0, l1: float = 0.0) -> None:
+    """Fused SAGA triple-axpy update (kernel K6). Non-zero l2/l1: prox-SAGA
+    step in the same kernel; the penalty never enters alpha_bar."""
     if w.is_cuda:
         mod = _require_hip("saga_update")
         if mod is not None:
             mod.saga_update(w, g, alpha_bar, float(gamma), float(inv_batch),
-                            float(inv_N))
+                            float(inv_N), float(l2), float(l1))
             return
-    torch_ref.saga_update(w, g, alpha_bar, gamma, inv_batch, inv_N)
+    torch_ref.saga_update(w, g, alpha_bar, gamma, inv_batch, inv_N, l2=l2,
+                          l1=l1)
 
 
 def objective_sweep(X: torch.Tensor, y: torch.Tensor, W: torch.Tensor,
-                    objective: str = "lsq") -> torch.Tensor:
+                    objective: str = "lsq", *, l2: float = 0.0,
+                    l1: float = 0.0) -> torch.Tensor:
     """Objective of stacked iterates (K7). GEMM-shaped: goes through the
     library GEMM (hipBLASLt via torch.matmul) on GPU — a plain GEMM is
     library territory, only the fused hot ops are hand-written."""
-    return torch_ref.objective_sweep(X, y, W, objective)
+    return torch_ref.objective_sweep(X, y, W, objective, l2=l2, l1=l1)
 
 
 def objective_sweep_csr(indptr, indices, values, y, W, objective="lsq",
-                        N_total=None) -> torch.Tensor:
+                        N_total=None, *, l2: float = 0.0,
+                        l1: float = 0.0) -> torch.Tensor:
     return torch_ref.objective_sweep_csr(indptr, indices, values, y, W,
-                                         objective, N_total)
+                                         objective, N_total, l2=l2, l1=l1)

@@ -169,15 +169,17 @@ def spill_refresh(alpha_dev, alpha_pinned, y, rowlist, ylist, cnt, cap, *,
                            _stream())
 
 
-def sgd_update(w, g, gamma_k, inv_batch) -> None:
+def sgd_update(w, g, gamma_k, inv_batch, l2=0.0, l1=0.0) -> None:
     _chk(w, "w", torch.float32)
     _chk(g, "g", torch.float32)
     _hip_core.sgd_update(w.data_ptr(), g.data_ptr(), gamma_k, inv_batch,
-                         int(w.numel()), _stream())
+                         int(w.numel()), _stream(), l2, l1)
 
 
-def saga_update(w, g, alpha_bar, gamma, inv_batch, inv_N) -> None:
+def saga_update(w, g, alpha_bar, gamma, inv_batch, inv_N, l2=0.0,
+                l1=0.0) -> None:
     _chk(w, "w", torch.float32)
     _chk(alpha_bar, "alpha_bar", torch.float32)
     _hip_core.saga_update(w.data_ptr(), g.data_ptr(), alpha_bar.data_ptr(),
-                          gamma, inv_batch, inv_N, int(w.numel()), _stream())
+                          gamma, inv_batch, inv_N, int(w.numel()), _stream(),
+                          l2, l1)

@@ -128,13 +128,14 @@ def saga_grad_csr(indptr: torch.Tensor, indices: torch.Tensor,
 
 
 def objective_sweep(X: torch.Tensor, y: torch.Tensor, W: torch.Tensor,
-                    objective: str = "lsq", batch_rows: int = 262144
-                    ) -> torch.Tensor:
+                    objective: str = "lsq", batch_rows: int = 262144,
+                    l2: float = 0.0, l1: float = 0.0) -> torch.Tensor:
     """Objective of each of T logged iterates in one dataset pass.
 
     W is [T, d] (stacked iterates — the reference computes all logged
     objectives in a single job, SparkASGDThread.scala:389-398). Returns [T]
-    fp64. lsq: sum((X w_t - y)^2)/N; logistic: mean log-loss."""
+    fp64. lsq: sum((X w_t - y)^2)/N; logistic: mean log-loss. Non-zero
+    l2/l1 add ``penalty(W, objective, l2, l1)``."""
     T = W.shape[0]
     N = X.shape[0]
     out = torch.zeros(T, dtype=torch.float64, device=X.device)
@@ -151,13 +152,17 @@ def objective_sweep(X: torch.Tensor, y: torch.Tensor, W: torch.Tensor,
         else:
             zy = Z * (2.0 * yb[:, None] - 1.0)
             out += torch.nn.functional.softplus(-zy).double().sum(dim=0)
-    return out / N
+    out = out / N
+    if l2 != 0.0 or l1 != 0.0:
+        out = out + penalty(W, objective, l2, l1).to(out.device)
+    return out
 
 
 def objective_sweep_csr(indptr: torch.Tensor, indices: torch.Tensor,
                         values: torch.Tensor, y: torch.Tensor,
                         W: torch.Tensor, objective: str = "lsq",
-                        N_total: Optional[int] = None) -> torch.Tensor:
+                        N_total: Optional[int] = None, l2: float = 0.0,
+                        l1: float = 0.0) -> torch.Tensor:
     """CSR objective sweep via torch.sparse mm."""
     n_rows = indptr.shape[0] - 1
     N = N_total if N_total is not None else n_rows
@@ -170,23 +175,63 @@ def objective_sweep_csr(indptr: torch.Tensor, indices: torch.Tensor,
     else:
         zy = Z * (2.0 * yb[:, None] - 1.0)
         out = torch.nn.functional.softplus(-zy).double().sum(dim=0)
-    return out / N
+    out = out / N
+    if l2 != 0.0 or l1 != 0.0:
+        out = out + penalty(W, objective, l2, l1).to(out.device)
+    return out
+
+
+def penalty(W: torch.Tensor, objective: str, l2: float,
+            l1: float) -> torch.Tensor:
+    """Elastic-net term of the REPORTED objective, per stacked iterate, fp64:
+    c*((l2/2)*||w_t||^2 + l1*||w_t||_1). c = 2 for lsq (the sweep's lsq value
+    is sum((x.w-y)^2)/N, twice the (1/2)(.)^2 loss whose gradient the kernels
+    use), 1 for logistic — so the reported number is a constant multiple of
+    the minimised F."""
+    c = 2.0 if objective == "lsq" else 1.0
+    Wd = W.double()
+    return c * (0.5 * float(l2) * (Wd * Wd).sum(dim=1)
+                + float(l1) * Wd.abs().sum(dim=1))
+
+
+def _reg_step(w: torch.Tensor, ghat: torch.Tensor, eta: float, l2: float,
+              l1: float) -> None:
+    """One regularised step, in place:
+    v = w - eta*(ghat + l2*w); w = soft_threshold(v, eta*l1), clipped
+    elements exactly +0.0."""
+    v = w - eta * (ghat + l2 * w)
+    t = eta * l1
+    w.copy_(torch.where(v > t, v - t,
+                        torch.where(v < -t, v + t, torch.zeros_like(v))))
 
 
 def sgd_update(w: torch.Tensor, g: torch.Tensor, gamma_k: float,
-               inv_batch: float) -> None:
+               inv_batch: float, *, l2: float = 0.0, l1: float = 0.0) -> None:
     """Fused scale+axpy weight update, in place:
     w -= gamma_k * (g * inv_batch). Reference updater thread
-    SparkASGDThread.scala:188-192 (scalOp + axpyOp)."""
+    SparkASGDThread.scala:188-192 (scalOp + axpyOp). With l2/l1 non-zero the
+    step is the decay + soft-threshold of _reg_step (eta = gamma_k,
+    ghat = inv_batch*g)."""
+    if l2 != 0.0 or l1 != 0.0:
+        _reg_step(w, inv_batch * g.to(w.dtype), gamma_k, l2, l1)
+        return
     w.add_(g.to(w.dtype), alpha=-(gamma_k * inv_batch))
 
 
 def saga_update(w: torch.Tensor, g: torch.Tensor, alpha_bar: torch.Tensor,
-                gamma: float, inv_batch: float, inv_N: float) -> None:
+                gamma: float, inv_batch: float, inv_N: float, *,
+                l2: float = 0.0, l1: float = 0.0) -> None:
     """Fused SAGA triple-axpy, in place (reference
     SparkASAGAThread.scala:217-220):
-    w -= gamma * (g*inv_batch); w -= gamma*alpha_bar; alpha_bar += g*inv_N."""
+    w -= gamma * (g*inv_batch); w -= gamma*alpha_bar; alpha_bar += g*inv_N.
+    With l2/l1 non-zero this is prox-SAGA: eta = gamma,
+    ghat = inv_batch*g + alpha_bar_old; the penalty stays out of alpha_bar."""
     gf = g.float()
+    if l2 != 0.0 or l1 != 0.0:
+        _reg_step(w, inv_batch * gf.to(w.dtype) + alpha_bar.to(w.dtype),
+                  gamma, l2, l1)
+        alpha_bar.add_(gf, alpha=inv_N)
+        return
     w.add_(gf.to(w.dtype), alpha=-(gamma * inv_batch))
     w.add_(alpha_bar.to(w.dtype), alpha=-gamma)
     alpha_bar.add_(gf, alpha=inv_N)

@@ -139,10 +139,12 @@ def final_report(cfg: EngineConfig, res: RunResult, data, sparse: bool,
         if sparse:
             indptr, indices, values, y = data
             obj = ops.objective_sweep_csr(indptr, indices, values, y, W,
-                                          cfg.objective, N_total=cfg.N)
+                                          cfg.objective, N_total=cfg.N,
+                                          l2=cfg.l2, l1=cfg.l1)
         else:
             X, y = data
-            obj = ops.objective_sweep(X, y, W, cfg.objective)
+            obj = ops.objective_sweep(X, y, W, cfg.objective, l2=cfg.l2,
+                                      l1=cfg.l1)
         logfmt.objective_lines(
             (t_ms, float(o)) for (t_ms, _), o in zip(res.opt_vars, obj))
     else:

@@ -12,6 +12,7 @@
 #include <pybind11/stl.h>
 
 #include <hip/hip_runtime.h>
+#include <cmath>
 #include <cstdint>
 #include <stdexcept>
 #include <string>
@@ -51,9 +52,10 @@ void launch_saga_grad_csr(const int*, const int*, const void*, const float*,
                           const float*, float*, float*, int*, int*, float*,
                           int*, const int*, int, long, uint64_t, uint32_t,
                           uint64_t, double, int, int, hipStream_t);
-void launch_sgd_update(float*, const float*, float, float, int, hipStream_t);
+void launch_sgd_update(float*, const float*, float, float, int, float, float,
+                       hipStream_t);
 void launch_saga_update(float*, const float*, float*, float, float, float,
-                        int, hipStream_t);
+                        int, float, float, hipStream_t);
 void launch_saga_commit(float*, const int*, const float*, int, hipStream_t);
 void launch_alpha_gather(float*, const float*, const int*, const int*, int,
                          hipStream_t);
@@ -62,9 +64,10 @@ void launch_sgd_update_fused(float*, float*, int*, float, float, int, int,
 void launch_saga_update_fused(float*, float*, float*, int*, float, float,
                               float, int, hipStream_t);
 int query_dense_kernel(int, int, int, int, int*);
+int query_update_kernel(int, int, int, int*);
 void launch_multi_update(float*, float* const*, float* const*, float*, float,
                          float, float, int, const MultiUpdateArgs*, int,
-                         hipStream_t);
+                         float, float, hipStream_t);
 }
 
 static void check(hipError_t err, const char* what) {
@@ -183,20 +186,26 @@ PYBIND11_MODULE(_hip_core, m) {
           check(hipGetLastError(), "saga_grad_csr launch");
         });
 
+  // l2 / l1 trail with defaults: the pre-regularisation call shapes work
   m.def("sgd_update", [](uintptr_t w, uintptr_t g, float gamma_k,
-                         float inv_batch, int d, uintptr_t stream) {
-    launch_sgd_update((float*)w, (const float*)g, gamma_k, inv_batch, d,
-                      (hipStream_t)stream);
+                         float inv_batch, int d, uintptr_t stream, float l2,
+                         float l1) {
+    launch_sgd_update((float*)w, (const float*)g, gamma_k, inv_batch, d, l2,
+                      l1, (hipStream_t)stream);
     check(hipGetLastError(), "sgd_update launch");
-  });
+  }, py::arg("w"), py::arg("g"), py::arg("gamma_k"), py::arg("inv_batch"),
+     py::arg("d"), py::arg("stream"), py::arg("l2") = 0.f,
+     py::arg("l1") = 0.f);
 
   m.def("saga_update", [](uintptr_t w, uintptr_t g, uintptr_t ab, float gamma,
                           float inv_batch, float inv_N, int d,
-                          uintptr_t stream) {
+                          uintptr_t stream, float l2, float l1) {
     launch_saga_update((float*)w, (const float*)g, (float*)ab, gamma,
-                       inv_batch, inv_N, d, (hipStream_t)stream);
+                       inv_batch, inv_N, d, l2, l1, (hipStream_t)stream);
     check(hipGetLastError(), "saga_update launch");
-  });
+  }, py::arg("w"), py::arg("g"), py::arg("alpha_bar"), py::arg("gamma"),
+     py::arg("inv_batch"), py::arg("inv_N"), py::arg("d"), py::arg("stream"),
+     py::arg("l2") = 0.f, py::arg("l1") = 0.f);
 
   m.def("saga_commit", [](uintptr_t alpha, uintptr_t idx, uintptr_t e, int n,
                           uintptr_t stream) {
@@ -259,17 +268,28 @@ PYBIND11_MODULE(_hip_core, m) {
   // Direct launch of the native engine's batched update kernel (tests).
   // g_ptrs / wbuf_ptrs are the per-worker device buffers (the engine's
   // g_tab / wbuf_tab); gw / sw index them; gw entries must be distinct.
-  // Synchronous: returns after the kernel has finished.
+  // Synchronous: returns after the kernel has finished. eta / l2 / l1
+  // (regularised form) trail with defaults; eta is the per-gradient bare
+  // ASGD step and is required, one per gradient, when algo == 0 and a
+  // penalty is non-zero.
   m.def("multi_update",
         [](uintptr_t w, std::vector<uintptr_t> g_ptrs,
            std::vector<uintptr_t> wbuf_ptrs, uintptr_t alpha_bar, float gamma,
            float inv_batch, float inv_N, int d, int algo,
            std::vector<int> gw, std::vector<int> sw,
-           std::vector<float> scale, uintptr_t stream) {
+           std::vector<float> scale, uintptr_t stream,
+           std::vector<float> eta, float l2, float l1) {
           if (gw.size() > MU_MAX || sw.size() > MU_MAX)
             throw std::runtime_error("multi_update: batch exceeds MU_MAX");
           if (algo == 0 && scale.size() != gw.size())
             throw std::runtime_error("multi_update: len(scale) != len(gw)");
+          if (!(l2 >= 0.f) || !(l1 >= 0.f) || std::isinf(l2) ||
+              std::isinf(l1))
+            throw std::runtime_error(
+                "multi_update: l2/l1 must be finite and non-negative");
+          const bool reg = l2 != 0.f || l1 != 0.f;
+          if (reg && algo == 0 && eta.size() != gw.size())
+            throw std::runtime_error("multi_update: len(eta) != len(gw)");
           MultiUpdateArgs a{};
           a.n = (int)gw.size();
           a.m = (int)sw.size();
@@ -285,6 +305,7 @@ PYBIND11_MODULE(_hip_core, m) {
                 throw std::runtime_error("multi_update: duplicate worker");
             a.gw[j] = gw[j];
             if (algo == 0) a.scale[j] = scale[j];
+            if (algo == 0 && reg) a.eta[j] = eta[j];
           }
           for (int j = 0; j < a.m; ++j) {
             if (sw[j] < 0 || (size_t)sw[j] >= wbuf_ptrs.size())
@@ -308,14 +329,41 @@ PYBIND11_MODULE(_hip_core, m) {
             launch_multi_update((float*)w, (float* const*)g_tab,
                                 (float* const*)wbuf_tab, (float*)alpha_bar,
                                 gamma, inv_batch, inv_N, d, &a, vec4 ? 1 : 0,
-                                (hipStream_t)stream);
+                                l2, l1, (hipStream_t)stream);
             e = hipGetLastError();
           }
           if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
           (void)hipFree(tabs);
           check(e, "multi_update");
           return vec4;
-        });
+        },
+        py::arg("w"), py::arg("g_ptrs"), py::arg("wbuf_ptrs"),
+        py::arg("alpha_bar"), py::arg("gamma"), py::arg("inv_batch"),
+        py::arg("inv_N"), py::arg("d"), py::arg("algo"), py::arg("gw"),
+        py::arg("sw"), py::arg("scale"), py::arg("stream"),
+        py::arg("eta") = std::vector<float>{}, py::arg("l2") = 0.f,
+        py::arg("l1") = 0.f);
+
+  // Compiled register / scratch / LDS use of the batched and the
+  // sync-round update kernels: [vec4][reg] instantiations by name.
+  m.def("update_kernel_info", []() {
+    py::dict out;
+    for (int k = 0; k < 8; ++k) {
+      int v[3] = {0};
+      check((hipError_t)query_update_kernel(k >> 2, (k >> 1) & 1, k & 1, v),
+            "update_kernel_info");
+      py::dict e;
+      e["num_regs"] = v[0];
+      e["local_size_bytes"] = v[1];
+      e["shared_size_bytes"] = v[2];
+      std::string name = (k >> 2) ? "sync_round_update_kernel"
+                                  : "multi_update_kernel";
+      name += std::string("<") + (((k >> 1) & 1) ? "true" : "false") + "," +
+              ((k & 1) ? "true" : "false") + ">";
+      out[py::str(name)] = e;
+    }
+    return out;
+  });
 
   register_libsvm(m);
   register_native_engine(m);

@@ -124,16 +124,17 @@ void launch_saga_grad_csr_flag(const int*, const int*, const void*,
                                long, uint64_t, uint32_t, uint64_t, double,
                                int, int, hipStream_t, unsigned long long*,
                                unsigned long long, unsigned long long*);
-void launch_sgd_update(float*, const float*, float, float, int, hipStream_t);
+void launch_sgd_update(float*, const float*, float, float, int, float, float,
+                       hipStream_t);
 void launch_saga_update(float*, const float*, float*, float, float, float,
-                        int, hipStream_t);
+                        int, float, float, hipStream_t);
 void launch_saga_commit(float*, const int*, const float*, int, hipStream_t);
 void launch_sgd_update_zero(float*, float*, float, float, int, hipStream_t);
 void launch_saga_update_zero(float*, float*, float*, float, float, float,
                              int, hipStream_t);
 void launch_multi_update(float*, float* const*, float* const*, float*, float,
                          float, float, int, const MultiUpdateArgs*, int,
-                         hipStream_t);
+                         float, float, hipStream_t);
 void launch_saga_commit_devn(float*, const int*, const float*, const int*,
                              int, hipStream_t);
 void launch_scan_rows(const float*, int*, float*, int*, const int*, long,
@@ -142,7 +143,8 @@ void launch_alpha_gather(float*, const float*, const int*, const int*, int,
                          hipStream_t);
 void launch_sync_round_update(float*, float* const*, int* const*, float*,
                               float*, int*, int, int, int, float, float,
-                              float, float, int, hipStream_t);
+                              float, float, int, float, float, float,
+                              hipStream_t);
 }
 
 namespace {
@@ -235,6 +237,7 @@ struct EngineCfg {
   long snap_every = 0;       // optVars cadence (reference printer_freq)
   uintptr_t snap_ring = 0;   // [snap_cap][d] device ring
   long snap_cap = 0;
+  double l2 = 0.0, l1 = 0.0;  // elastic-net penalties (0/0: legacy kernels)
 };
 
 double now_s() {
@@ -614,7 +617,8 @@ struct NativeEngine {
       launch_multi_update((float*)w, (float* const*)g_tab_dev,
                           (float* const*)wbuf_tab_dev, (float*)alpha_bar,
                           (float)cfg.gamma, (float)inv_batch, (float)inv_N,
-                          cfg.d, &mu, mu_vec4 ? 1 : 0, sstream);
+                          cfg.d, &mu, mu_vec4 ? 1 : 0, (float)cfg.l2,
+                          (float)cfg.l1, sstream);
       HIP_CHECK(hipGetLastError());
       launched = true;
       mu.n = 0;
@@ -635,6 +639,7 @@ struct NativeEngine {
     if (cfg.algo == 0) {
       const double gamma_k = cfg.gamma / std::sqrt((double)(k / cfg.P + 1));
       mu.scale[mu.n] = (float)(gamma_k * inv_batch);
+      mu.eta[mu.n] = (float)gamma_k;  // read by the regularised form only
     }
     // multi_update_kernel reads every g of the batch before it zeroes any:
     // a worker may appear only once per batch (it is redispatched, and can
@@ -1134,7 +1139,9 @@ struct NativeEngine {
                                (int* const*)ctr_tab_dev, (float*)alpha_bar,
                                snap_dst, sync_ticket_dev, cfg.P, cfg.d, mode,
                                scale, (float)cfg.gamma, (float)inv_bN,
-                               (float)inv_N, vec4 ? 1 : 0, sstream);
+                               (float)inv_N, vec4 ? 1 : 0,
+                               (float)(mode == 1 ? cfg.gamma : gamma_k),
+                               (float)cfg.l2, (float)cfg.l1, sstream);
       HIP_CHECK(hipGetLastError());
       HIP_CHECK(hipEventRecord(update_ev, sstream));
       sync_wait_round(k, std::max(t_submit, t_release));
@@ -1191,6 +1198,12 @@ void fill_engine(NativeEngine& eng, py::dict c, py::list workers,
   cfg.mark_hi = py::cast<long>(c["mark_hi"]);
   cfg.max_wall_s = py::cast<double>(c["max_wall_s"]);
   if (c.contains("stall_s")) cfg.stall_s = py::cast<double>(c["stall_s"]);
+  if (c.contains("l2")) cfg.l2 = py::cast<double>(c["l2"]);
+  if (c.contains("l1")) cfg.l1 = py::cast<double>(c["l1"]);
+  if (!(cfg.l2 >= 0.0) || !(cfg.l1 >= 0.0) || std::isinf(cfg.l2) ||
+      std::isinf(cfg.l1))
+    throw std::runtime_error(
+        "native engine: l2/l1 must be finite and non-negative");
   cfg.snap_every = py::cast<long>(c["snap_every"]);
   cfg.snap_ring = py::cast<uintptr_t>(c["snap_ring"]);
   cfg.snap_cap = py::cast<long>(c["snap_cap"]);

@@ -1045,27 +1045,81 @@ __global__ void alpha_gather_wave_kernel(
 }
 
 
+// ------------------------------------------------- elastic-net step (REG)
+// The REG=true forms of the update kernels minimise
+//   F(w) = (1/N) sum_i f_i(w) + (l2/2)|w|^2 + l1*|w|_1
+// with one step per applied update, on the value already in a register:
+//   v = w - eta*(ghat + l2*w)                  L2: exact gradient step
+//   w = v > t ? v - t : (v < -t ? v + t : +0)  L1: prox, t = eta*l1
+// written as v = fma(-step, g, dec*w) with dec = fma(-eta, l2, 1) — for
+// l1 = 0 literally MLlib's SquaredL2Updater w*(1 - eta*l2) - eta*ghat, for
+// l2 = 0 its L1Updater. Every product and sum below is an explicit
+// single-rounding intrinsic, so the rounding count the tests assume does
+// not depend on the contraction mode. No extra global load or store: the
+// REG=false instantiations keep the old bodies and the old bits.
+__device__ __forceinline__ float reg_dec(float eta, float l2) {
+  return fmaf(-eta, l2, 1.f);
+}
+__device__ __forceinline__ float reg_thr(float eta, float l1) {
+  return __fmul_rn(eta, l1);
+}
+// |v| - t is computed unconditionally and its sign decides (v - t for
+// v > t and v + t for v < -t are +-(|v| - t) with the same single rounding;
+// anything else, a NaN included, is +0): two selects, no divergent branch —
+// the nested-ternary form compiled to an exec-mask branch per element.
+__device__ __forceinline__ float reg_prox(float v, float t) {
+  const float a = __fsub_rn(fabsf(v), t);
+  return a > 0.f ? copysignf(a, v) : 0.f;
+}
+// v for a step whose data term is step*g
+__device__ __forceinline__ float reg_step(float w, float g, float step,
+                                          float dec, float t) {
+  return reg_prox(fmaf(-step, g, __fmul_rn(dec, w)), t);
+}
+
 // ---------------------------------------------------------------- K5/K6
 
+template <bool REG>
 __global__ void sgd_update_kernel(float* __restrict__ w,
                                   const float* __restrict__ g, float gamma_k,
-                                  float inv_batch, int d) {
+                                  float inv_batch, int d, float l2,
+                                  float l1) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < d) w[i] -= gamma_k * inv_batch * g[i];
+  if constexpr (REG) {
+    if (i < d)
+      w[i] = reg_step(w[i], g[i], __fmul_rn(gamma_k, inv_batch),
+                      reg_dec(gamma_k, l2), reg_thr(gamma_k, l1));
+  } else {
+    if (i < d) w[i] -= gamma_k * inv_batch * g[i];
+  }
 }
 
 // w -= gamma*(inv_batch*g + alpha_bar_old); alpha_bar += inv_N*g
 // (order matches reference SparkASAGASync.scala:300-304 /
 //  SparkASAGAThread.scala:217-220: w reads the OLD alpha_bar).
+// REG: prox-SAGA — ghat = inv_batch*g + alpha_bar_old, eta = gamma; the
+// penalty stays out of alpha_bar (and out of the history table).
+template <bool REG>
 __global__ void saga_update_kernel(float* __restrict__ w,
                                    const float* __restrict__ g,
                                    float* __restrict__ alpha_bar, float gamma,
-                                   float inv_batch, float inv_N, int d) {
+                                   float inv_batch, float inv_N, int d,
+                                   float l2, float l1) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < d) {
-    const float gi = g[i];
-    w[i] -= gamma * (inv_batch * gi + alpha_bar[i]);
-    alpha_bar[i] += inv_N * gi;
+  if constexpr (REG) {
+    if (i < d) {
+      const float gi = g[i];
+      const float ab = alpha_bar[i];
+      w[i] = reg_step(w[i], fmaf(inv_batch, gi, ab), gamma,
+                      reg_dec(gamma, l2), reg_thr(gamma, l1));
+      alpha_bar[i] = fmaf(inv_N, gi, ab);
+    }
+  } else {
+    if (i < d) {
+      const float gi = g[i];
+      w[i] -= gamma * (inv_batch * gi + alpha_bar[i]);
+      alpha_bar[i] += inv_N * gi;
+    }
   }
 }
 
@@ -1170,12 +1224,25 @@ __device__ __forceinline__ void mu_saga(float& w, float& ab, float g,
   w -= gamma * (inv_batch * g + ab);
   ab += inv_N * g;
 }
+// regularised forms (REG): one decay-and-threshold step per gradient
+__device__ __forceinline__ void mu_saga_reg(float& w, float& ab, float g,
+                                            float gamma, float inv_batch,
+                                            float inv_N, float dec, float t) {
+  w = reg_step(w, fmaf(inv_batch, g, ab), gamma, dec, t);
+  ab = fmaf(inv_N, g, ab);
+}
 
-template <bool VEC4>
+// REG applies the elastic-net step (above) once per accepted gradient, in
+// batch order — n gradients are n decay-and-threshold steps, the same as n
+// singleton launches — with eta = a.eta[j] (ASGD) or gamma (ASAGA). Only
+// the apply stage's arithmetic differs: same global loads, same stores, so
+// the snapshot targets receive the post-threshold w.
+template <bool VEC4, bool REG>
 __global__ __launch_bounds__(MU_BLOCK) void multi_update_kernel(
     float* __restrict__ w, float* const* __restrict__ g_tab,
     float* const* __restrict__ wbuf_tab, float* __restrict__ alpha_bar,
-    float gamma, float inv_batch, float inv_N, int d, MultiUpdateArgs a) {
+    float gamma, float inv_batch, float inv_N, int d, float l2, float l1,
+    MultiUpdateArgs a) {
   using V = typename std::conditional<VEC4, float4, float>::type;
   const int nel = VEC4 ? d >> 2 : d;
   const V zero = V{};
@@ -1186,6 +1253,17 @@ __global__ __launch_bounds__(MU_BLOCK) void multi_update_kernel(
     if (a.algo != 0) ab = reinterpret_cast<const V*>(alpha_bar)[i];
     for (int j0 = 0; j0 < a.n; j0 += MU_CHUNK) {
       V gv[MU_CHUNK];
+      // REG: the chunk's per-gradient steps, fetched with the gradients
+      // (j0 + c < MU_MAX: in bounds, entries past n are never applied) so
+      // the apply stage waits for no kernel-argument load per gradient
+      [[maybe_unused]] float sc_c[MU_CHUNK], eta_c[MU_CHUNK];
+      if constexpr (REG) {
+#pragma unroll
+        for (int c = 0; c < MU_CHUNK; ++c) {
+          sc_c[c] = a.scale[j0 + c];
+          eta_c[c] = a.eta[j0 + c];
+        }
+      }
 #pragma unroll
       for (int c = 0; c < MU_CHUNK; ++c) {
         const int j = min(j0 + c, a.n - 1);
@@ -1195,7 +1273,32 @@ __global__ __launch_bounds__(MU_BLOCK) void multi_update_kernel(
       for (int c = 0; c < MU_CHUNK; ++c) {
         const int j = j0 + c;
         if (j < a.n) {
-          if constexpr (VEC4) {
+          if constexpr (REG) {
+            const float eta = a.algo == 0 ? eta_c[c] : gamma;
+            const float dec = reg_dec(eta, l2), t = reg_thr(eta, l1);
+            if constexpr (VEC4) {
+              if (a.algo == 0) {
+                const float sc = sc_c[c];
+                wi.x = reg_step(wi.x, gv[c].x, sc, dec, t);
+                wi.y = reg_step(wi.y, gv[c].y, sc, dec, t);
+                wi.z = reg_step(wi.z, gv[c].z, sc, dec, t);
+                wi.w = reg_step(wi.w, gv[c].w, sc, dec, t);
+              } else {
+                mu_saga_reg(wi.x, ab.x, gv[c].x, gamma, inv_batch, inv_N,
+                            dec, t);
+                mu_saga_reg(wi.y, ab.y, gv[c].y, gamma, inv_batch, inv_N,
+                            dec, t);
+                mu_saga_reg(wi.z, ab.z, gv[c].z, gamma, inv_batch, inv_N,
+                            dec, t);
+                mu_saga_reg(wi.w, ab.w, gv[c].w, gamma, inv_batch, inv_N,
+                            dec, t);
+              }
+            } else {
+              if (a.algo == 0) wi = reg_step(wi, gv[c], sc_c[c], dec, t);
+              else mu_saga_reg(wi, ab, gv[c], gamma, inv_batch, inv_N, dec,
+                               t);
+            }
+          } else if constexpr (VEC4) {
             if (a.algo == 0) {
               const float sc = a.scale[j];
               mu_asgd(wi.x, gv[c].x, sc); mu_asgd(wi.y, gv[c].y, sc);
@@ -1236,8 +1339,14 @@ __global__ __launch_bounds__(MU_BLOCK) void multi_update_kernel(
 //   mode 2 mllib: w -= scale * s / max(n,1) (scale = gamma_k, host;
 //                 n = sum_p ctr_p[0], the round's ACTUAL sample count, read
 //                 here on the device — no D2H);
-//   snap_dst[i] = post-update w[i] when snap_dst != null (fused optVars
-//                 snapshot copy).
+//   REG: the same step with the elastic-net terms (helpers above), once
+//                 per round: v = dec*w - step*s (asgd/mllib, step = the
+//                 scale above) or dec*w - gamma*(inv_batch*s + alpha_bar)
+//                 (asaga), then the soft-threshold. ``eta`` is the bare
+//                 step (gamma_k; gamma for asaga) — separate from scale,
+//                 which mllib mode divides by the sample count;
+//   snap_dst[i] = post-update (REG: post-threshold) w[i] when snap_dst !=
+//                 null (fused optVars snapshot copy).
 // Everything read here (g_p, ctr_p) was written by the gradient kernel that
 // precedes this one ON THE SAME STREAM, so plain loads are correct — unlike
 // the async path, whose cross-stream consumers need agent-scope atomics.
@@ -1247,12 +1356,13 @@ __global__ __launch_bounds__(MU_BLOCK) void multi_update_kernel(
 // reset races no read.
 #define SRU_BLOCK 64
 
-template <bool VEC4>
+template <bool VEC4, bool REG>
 __global__ __launch_bounds__(SRU_BLOCK) void sync_round_update_kernel(
     float* __restrict__ w, float* const* __restrict__ g_tab,
     int* const* __restrict__ ctr_tab, float* __restrict__ alpha_bar,
     float* __restrict__ snap_dst, int* __restrict__ ticket, int P, int d,
-    int mode, float scale, float gamma, float inv_batch, float inv_N) {
+    int mode, float scale, float gamma, float inv_batch, float inv_N,
+    float eta, float l2, float l1) {
   __shared__ int n_sh;
   if (mode == 2) {  // uniform per launch
     if (threadIdx.x == 0) {
@@ -1263,6 +1373,8 @@ __global__ __launch_bounds__(SRU_BLOCK) void sync_round_update_kernel(
     __syncthreads();
     scale = scale / (float)max(n_sh, 1);
   }
+  [[maybe_unused]] const float dec = REG ? reg_dec(eta, l2) : 1.f;
+  [[maybe_unused]] const float thr = REG ? reg_thr(eta, l1) : 0.f;
   const int stride = gridDim.x * SRU_BLOCK;
   if (VEC4) {
     const int n4 = d >> 2;
@@ -1277,7 +1389,21 @@ __global__ __launch_bounds__(SRU_BLOCK) void sync_round_update_kernel(
         reinterpret_cast<float4*>(g_tab[p])[i] =
             make_float4(0.f, 0.f, 0.f, 0.f);
       float4 wi = reinterpret_cast<float4*>(w)[i];
-      if (mode == 1) {
+      if constexpr (REG) {
+        if (mode == 1) {
+          float4 ab = reinterpret_cast<float4*>(alpha_bar)[i];
+          mu_saga_reg(wi.x, ab.x, s.x, gamma, inv_batch, inv_N, dec, thr);
+          mu_saga_reg(wi.y, ab.y, s.y, gamma, inv_batch, inv_N, dec, thr);
+          mu_saga_reg(wi.z, ab.z, s.z, gamma, inv_batch, inv_N, dec, thr);
+          mu_saga_reg(wi.w, ab.w, s.w, gamma, inv_batch, inv_N, dec, thr);
+          reinterpret_cast<float4*>(alpha_bar)[i] = ab;
+        } else {
+          wi.x = reg_step(wi.x, s.x, scale, dec, thr);
+          wi.y = reg_step(wi.y, s.y, scale, dec, thr);
+          wi.z = reg_step(wi.z, s.z, scale, dec, thr);
+          wi.w = reg_step(wi.w, s.w, scale, dec, thr);
+        }
+      } else if (mode == 1) {
         float4 ab = reinterpret_cast<float4*>(alpha_bar)[i];
         wi.x -= gamma * (inv_batch * s.x + ab.x);
         wi.y -= gamma * (inv_batch * s.y + ab.y);
@@ -1300,7 +1426,15 @@ __global__ __launch_bounds__(SRU_BLOCK) void sync_round_update_kernel(
       for (int p = 0; p < P; ++p) s += g_tab[p][i];
       for (int p = 0; p < P; ++p) g_tab[p][i] = 0.f;
       float wi = w[i];
-      if (mode == 1) {
+      if constexpr (REG) {
+        if (mode == 1) {
+          float ab = alpha_bar[i];
+          mu_saga_reg(wi, ab, s, gamma, inv_batch, inv_N, dec, thr);
+          alpha_bar[i] = ab;
+        } else {
+          wi = reg_step(wi, s, scale, dec, thr);
+        }
+      } else if (mode == 1) {
         const float ab = alpha_bar[i];
         wi -= gamma * (inv_batch * s + ab);
         alpha_bar[i] = ab + inv_N * s;
@@ -1901,19 +2035,32 @@ void launch_saga_grad_csr_flag(
 #undef CSR_SLAUNCH
 }
 
+// l2 == l1 == 0 dispatches to the REG=false instantiation (the unchanged
+// body): the unregularised bits never depend on x*1.0 or x-0.0.
 void launch_sgd_update(float* w, const float* g, float gamma_k,
-                       float inv_batch, int d, hipStream_t stream) {
+                       float inv_batch, int d, float l2, float l1,
+                       hipStream_t stream) {
   const int grid = (d + 255) / 256;
-  hipLaunchKernelGGL(sgd_update_kernel, dim3(grid), dim3(256), 0, stream, w,
-                     g, gamma_k, inv_batch, d);
+  if (l2 != 0.f || l1 != 0.f)
+    hipLaunchKernelGGL(sgd_update_kernel<true>, dim3(grid), dim3(256), 0,
+                       stream, w, g, gamma_k, inv_batch, d, l2, l1);
+  else
+    hipLaunchKernelGGL(sgd_update_kernel<false>, dim3(grid), dim3(256), 0,
+                       stream, w, g, gamma_k, inv_batch, d, l2, l1);
 }
 
 void launch_saga_update(float* w, const float* g, float* alpha_bar,
                         float gamma, float inv_batch, float inv_N, int d,
-                        hipStream_t stream) {
+                        float l2, float l1, hipStream_t stream) {
   const int grid = (d + 255) / 256;
-  hipLaunchKernelGGL(saga_update_kernel, dim3(grid), dim3(256), 0, stream, w,
-                     g, alpha_bar, gamma, inv_batch, inv_N, d);
+  if (l2 != 0.f || l1 != 0.f)
+    hipLaunchKernelGGL(saga_update_kernel<true>, dim3(grid), dim3(256), 0,
+                       stream, w, g, alpha_bar, gamma, inv_batch, inv_N, d,
+                       l2, l1);
+  else
+    hipLaunchKernelGGL(saga_update_kernel<false>, dim3(grid), dim3(256), 0,
+                       stream, w, g, alpha_bar, gamma, inv_batch, inv_N, d,
+                       l2, l1);
 }
 
 void launch_sgd_update_zero(float* w, float* g, float gamma_k,
@@ -1969,20 +2116,25 @@ void launch_saga_update_fused(float* w, float* g, float* alpha_bar,
 void launch_multi_update(float* w, float* const* g_tab,
                          float* const* wbuf_tab, float* alpha_bar,
                          float gamma, float inv_batch, float inv_N, int d,
-                         const MultiUpdateArgs* a, int vec4,
-                         hipStream_t stream) {
+                         const MultiUpdateArgs* a, int vec4, float l2,
+                         float l1, hipStream_t stream) {
   const int nel = vec4 ? d / 4 : d;
   int grid = (nel + MU_BLOCK - 1) / MU_BLOCK;
   if (grid > 4096) grid = 4096;
   if (grid < 1) grid = 1;
-  if (vec4)
-    hipLaunchKernelGGL(multi_update_kernel<true>, dim3(grid), dim3(MU_BLOCK),
-                       0, stream, w, g_tab, wbuf_tab, alpha_bar, gamma,
-                       inv_batch, inv_N, d, *a);
-  else
-    hipLaunchKernelGGL(multi_update_kernel<false>, dim3(grid),
-                       dim3(MU_BLOCK), 0, stream, w, g_tab, wbuf_tab,
-                       alpha_bar, gamma, inv_batch, inv_N, d, *a);
+  const bool reg = l2 != 0.f || l1 != 0.f;
+#define MU_LAUNCH(V, R)                                                      \
+  hipLaunchKernelGGL((multi_update_kernel<V, R>), dim3(grid),                \
+                     dim3(MU_BLOCK), 0, stream, w, g_tab, wbuf_tab,          \
+                     alpha_bar, gamma, inv_batch, inv_N, d, l2, l1, *a)
+  if (vec4) {
+    if (reg) MU_LAUNCH(true, true);
+    else MU_LAUNCH(true, false);
+  } else {
+    if (reg) MU_LAUNCH(false, true);
+    else MU_LAUNCH(false, false);
+  }
+#undef MU_LAUNCH
 }
 
 // One barrier round of the native engine's synchronous mode. The work is
@@ -1997,21 +2149,49 @@ void launch_sync_round_update(float* w, float* const* g_tab,
                               float* snap_dst, int* ticket, int P, int d,
                               int mode, float scale, float gamma,
                               float inv_batch, float inv_N, int vec4,
+                              float eta, float l2, float l1,
                               hipStream_t stream) {
   const int n = vec4 ? d / 4 : d;
   int grid = (n + SRU_BLOCK - 1) / SRU_BLOCK;
   if (grid > 1024) grid = 1024;
   if (grid < 1) grid = 1;
-  if (vec4)
-    hipLaunchKernelGGL(sync_round_update_kernel<true>, dim3(grid),
-                       dim3(SRU_BLOCK), 0, stream, w, g_tab, ctr_tab,
-                       alpha_bar, snap_dst, ticket, P, d, mode, scale, gamma,
-                       inv_batch, inv_N);
-  else
-    hipLaunchKernelGGL(sync_round_update_kernel<false>, dim3(grid),
-                       dim3(SRU_BLOCK), 0, stream, w, g_tab, ctr_tab,
-                       alpha_bar, snap_dst, ticket, P, d, mode, scale, gamma,
-                       inv_batch, inv_N);
+  const bool reg = l2 != 0.f || l1 != 0.f;
+#define SRU_LAUNCH(V, R)                                                     \
+  hipLaunchKernelGGL((sync_round_update_kernel<V, R>), dim3(grid),           \
+                     dim3(SRU_BLOCK), 0, stream, w, g_tab, ctr_tab,          \
+                     alpha_bar, snap_dst, ticket, P, d, mode, scale, gamma,  \
+                     inv_batch, inv_N, eta, l2, l1)
+  if (vec4) {
+    if (reg) SRU_LAUNCH(true, true);
+    else SRU_LAUNCH(true, false);
+  } else {
+    if (reg) SRU_LAUNCH(false, true);
+    else SRU_LAUNCH(false, false);
+  }
+#undef SRU_LAUNCH
+}
+
+// Compiled resource use of one update-kernel instantiation: sync = 0
+// multi_update_kernel<vec4, reg>, 1 sync_round_update_kernel<vec4, reg>.
+// out = {numRegs, localSizeBytes (scratch), sharedSizeBytes (static LDS)}.
+// Returns 0 or a hipError_t.
+int query_update_kernel(int sync, int vec4, int reg, int* out) {
+  const void* mu[4] = {(const void*)multi_update_kernel<false, false>,
+                       (const void*)multi_update_kernel<false, true>,
+                       (const void*)multi_update_kernel<true, false>,
+                       (const void*)multi_update_kernel<true, true>};
+  const void* sru[4] = {(const void*)sync_round_update_kernel<false, false>,
+                        (const void*)sync_round_update_kernel<false, true>,
+                        (const void*)sync_round_update_kernel<true, false>,
+                        (const void*)sync_round_update_kernel<true, true>};
+  const int k = (vec4 ? 2 : 0) + (reg ? 1 : 0);
+  hipFuncAttributes attr;
+  const hipError_t e = hipFuncGetAttributes(&attr, sync ? sru[k] : mu[k]);
+  if (e != hipSuccess) return (int)e;
+  out[0] = attr.numRegs;
+  out[1] = (int)attr.localSizeBytes;
+  out[2] = (int)attr.sharedSizeBytes;
+  return 0;
 }
 
 void launch_saga_commit_devn(float* alpha, const int* idx, const float* e,

@@ -13,4 +13,7 @@ struct MultiUpdateArgs {
   int gw[MU_MAX];        // worker id per gradient (indexes g_tab)
   int sw[MU_MAX];        // worker id per snapshot (indexes wbuf_tab)
   float scale[MU_MAX];   // ASGD: gamma_k * inv_batch per gradient
+  float eta[MU_MAX];     // ASGD, regularised form only: gamma_k per gradient
+                         // (scale has inv_batch folded in; the decay and the
+                         // soft-threshold need the bare step). 524 B in all.
 };
