@@ -32,8 +32,9 @@ SOURCES = [ROOT / "csrc" / "kernels.hip", ROOT / "csrc" / "bindings.cpp",
            ROOT / "csrc" / "libsvm_parser.cpp",
            ROOT / "csrc" / "engine_native.cpp",
            ROOT / "csrc" / "engine_resident.hip"]
+UPDATE_STEP = ROOT / "csrc" / "update_step.h"  # included by both extensions
 HEADERS = [ROOT / "csrc" / "philox.h", ROOT / "csrc" / "multi_update.h",
-           ROOT / "csrc" / "grad_wave.h"]
+           ROOT / "csrc" / "grad_wave.h", UPDATE_STEP]
 DIST_SRC = ROOT / "csrc" / "server_dist.cpp"
 DIST_HIP = ROOT / "csrc" / "dist_update.hip"
 DIST_DIR = ROOT / "asyncframework_amd" / "_dist_build"
@@ -60,6 +61,7 @@ def dist_src_hash() -> str:
     h.update(ARCH.encode())
     h.update(DIST_SRC.read_bytes())
     h.update(DIST_HIP.read_bytes())
+    h.update(UPDATE_STEP.read_bytes())
     return h.hexdigest()[:16]
 
 
@@ -116,8 +118,10 @@ def build_dist_core(force: bool = False, verbose: bool = True) -> Path:
         return out
     from torch.utils.cpp_extension import load
     DIST_DIR.mkdir(parents=True, exist_ok=True)
-    if force and out.exists():
-        out.unlink()  # torch load() otherwise reuses by its own mtime check
+    # torch load() otherwise reuses the .so by its own mtime check, and its
+    # ninja file does not track the header the .hip source includes
+    for stale in [out, *DIST_DIR.glob("*.o")]:
+        stale.unlink(missing_ok=True)
     load(name="_dist_core", sources=[str(DIST_SRC), str(DIST_HIP)],
          build_directory=str(DIST_DIR), verbose=verbose)
     _write_prov(dist_src_hash=cur)

@@ -79,20 +79,6 @@
 namespace py = pybind11;
 
 extern "C" {
-void launch_grad_dense(const void*, const float*, const float*, float*,
-                       float*, int*, const int*, long, int, uint64_t,
-                       uint32_t, uint64_t, double, int, int, hipStream_t);
-void launch_saga_grad_dense(const void*, const float*, const float*, float*,
-                            float*, float*, int*, int*, float*, int*,
-                            const int*, int, long, int, uint64_t, uint32_t,
-                            uint64_t, double, int, int, hipStream_t);
-void launch_grad_csr(const int*, const int*, const void*, const float*,
-                     const float*, float*, int*, const int*, long, uint64_t,
-                     uint32_t, uint64_t, double, int, int, hipStream_t);
-void launch_saga_grad_csr(const int*, const int*, const void*, const float*,
-                          const float*, float*, float*, int*, int*, float*,
-                          int*, const int*, int, long, uint64_t, uint32_t,
-                          uint64_t, double, int, int, hipStream_t);
 int query_grad_grid(long);
 void launch_grad_csr_wave(const void*, const void*, uint64_t, double, int,
                           int, int, hipStream_t);
@@ -124,14 +110,6 @@ void launch_saga_grad_csr_flag(const int*, const int*, const void*,
                                long, uint64_t, uint32_t, uint64_t, double,
                                int, int, hipStream_t, unsigned long long*,
                                unsigned long long, unsigned long long*);
-void launch_sgd_update(float*, const float*, float, float, int, float, float,
-                       hipStream_t);
-void launch_saga_update(float*, const float*, float*, float, float, float,
-                        int, float, float, hipStream_t);
-void launch_saga_commit(float*, const int*, const float*, int, hipStream_t);
-void launch_sgd_update_zero(float*, float*, float, float, int, hipStream_t);
-void launch_saga_update_zero(float*, float*, float*, float, float, float,
-                             int, hipStream_t);
 void launch_multi_update(float*, float* const*, float* const*, float*, float,
                          float, float, int, const MultiUpdateArgs*, int,
                          float, float, hipStream_t);

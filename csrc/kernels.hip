@@ -9,14 +9,23 @@
 //                        queue + register pipeline), scan_rows_kernel +
 //                        grad_dense_list_kernel (split form for the graph
 //                        engine's scan/compute overlap), and a generic
-//                        fallback for d > 2048 or d % 4 != 0.
+//                        fallback for d > 2048 or d % 4 != 0. The queue-fed
+//                        forms share ONE scan loop (scan_enqueue), ONE row
+//                        pipeline (pipe_drain) and ONE partials flush
+//                        (flush_partials).
 //   K2 grad_csr        — CSR SpMV-style gradient, wave-per-row
 //                        (reference sparse BLAS.scala:74-90,134-160).
 //   K3 saga_grad_*     — K1/K2 fused with the per-sample history gather and
 //                        staged scalar emit (SparkASAGAThread.scala:380-385).
 //   K5 sgd_update      — fused scale+axpy weight update (:188-192).
 //   K6 saga_update     — fused SAGA triple-axpy (:217-220).
+//                        K5/K6 arithmetic, plain and elastic-net, lives in
+//                        update_step.h (asgd_step / saga_step); the singleton,
+//                        batched (multi_update), sync-round, fused-graph and
+//                        reduce+update kernels all call it.
 //   K8 philox.h        — in-kernel counter-based Bernoulli mask.
+// Launchers: runtime (dtype, saga, ITERS, DEPTH, LPR, flags) become template
+// arguments through with_const / with_bool / with_xt_saga / with_pipe_shape.
 //
 // Design notes (MI355X, measured on hardware):
 //  * 64-wide wavefronts. ONE Philox eval decides FOUR consecutive rows
@@ -51,6 +60,7 @@
 #include <type_traits>
 #include "philox.h"
 #include "grad_wave.h"
+#include "update_step.h"
 
 #define WAVE 64
 #define BLOCK 256
@@ -277,11 +287,13 @@ __global__ __launch_bounds__(BLOCK) void grad_dense_kernel(
 // around every load with a vmcnt(0) (guide trap 4(c)). The accumulate pass
 // reuses the pipeline registers; X is read exactly once per sampled row.
 
+// Row-queue capacity, for every queue: the pipe kernels' LDS queue, the
+// standalone scan's and the list kernel's staging chunk.
 #define QCAP 2048
 
 // ---- pipelined-kernel shape selection: the ONE place that decides ITERS,
-// DEPTH and the occupancy hint. The launchers and the query_dense_kernel
-// binding both go through it.
+// DEPTH, the LDS sizes and the occupancy hint. The pipe, wave and list
+// launchers and the query_dense_kernel binding all go through it.
 //
 // Occupancy hint = second argument of __launch_bounds__ = minimum waves per
 // SIMD; a 256-thread block is one wave per SIMD, so the hint is also the
@@ -298,10 +310,25 @@ __global__ __launch_bounds__(BLOCK) void grad_dense_kernel(
 #define CU_LDS_BYTES 163840
 #define PIPE_WORK_VGPRS 76
 
+// LDS layout shared by the pipelined kernels, in carving order: w_lds[DPAD],
+// one gradient slab gacc[NW][DPAD] per wave, then the queue arrays. The
+// kernels carve smem with these same constants.
+#define PIPE_BLOCK 256
+#define PIPE_NW (PIPE_BLOCK / WAVE)
+constexpr int pipe_dpad(int iters) { return iters * 256; }  // padded d
+constexpr size_t slab_lds_bytes(int iters) {
+  return (size_t)(1 + PIPE_NW) * pipe_dpad(iters) * sizeof(float);
+}
+// pipe / wave: + yq (and SAGA's aq, eq), rowq, the queue counter
 constexpr size_t pipe_lds_bytes(int iters, bool saga) {
-  return (size_t)(1 + 4) * (iters * 256) * sizeof(float) +
+  return slab_lds_bytes(iters) +
          (size_t)QCAP * sizeof(float) * (saga ? 3 : 1) +
          (QCAP + 1) * sizeof(int);
+}
+// list: + yq, rowq
+constexpr size_t list_lds_bytes(int iters) {
+  return slab_lds_bytes(iters) +
+         (size_t)QCAP * (sizeof(float) + sizeof(int));
 }
 constexpr int occupancy_hint(size_t lds_bytes, int xt_bytes, int depth,
                              int iters) {
@@ -391,6 +418,139 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t row_rsrc(
                                            0x00020000);
 }
 
+// Scan phase, for every queue-fed kernel: the block walks its groups of RPB
+// rows (gi, gi + nblk, ...; one Philox eval decides four rows) and appends
+// the sampled row ids to rowq until the groups run out or one more group
+// might overflow the queue. Row ids only — a y[row] load per hit would
+// expose one global-load latency per scan iteration ahead of the
+// iteration's barrier. The caller barriers before it reads *qn.
+template <int RPB>
+__device__ __forceinline__ void scan_enqueue(
+    int* rowq, int* qn, int cap, long& gi, long ngroups, int nblk,
+    long n_rows, uint64_t seed, uint32_t round_k, uint64_t row_start,
+    uint32_t threshold, int take_all, int wave, int lane) {
+  while (true) {
+    __syncthreads();
+    if (gi >= ngroups || *qn >= cap - RPB) break;
+    const long base = gi * (long)RPB + (long)wave * ROWS_PER_WAVE;
+    if (base < n_rows) {
+      const uint4 x = philox_block4(
+          seed, round_k, (row_start + (uint64_t)base) / 4 + (uint64_t)lane);
+      const long rem = n_rows - base;
+      const long lrow = base + 4L * lane;
+      const uint32_t xs[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        if (4L * lane + i < rem && (take_all || xs[i] < threshold)) {
+          const int pos = atomicAdd(qn, 1);
+          rowq[pos] = (int)(lrow + i);
+        }
+      }
+    }
+    gi += nblk;
+  }
+}
+
+// Process phase, for every queue-fed kernel: the block's NW waves drain
+// rowq[0..nq) round-robin, each through a DEPTH-deep statically-unrolled
+// register pipeline of whole rows. Per row: z = x . w_lds, then
+// gw += coeff_of(q, z) * x, reusing the pipeline registers — X is read
+// exactly once per sampled row. Returns the number of rows this wave
+// processed. Only buffer loads and LDS traffic may happen in here and in
+// coeff_of: hipcc drains vmcnt(0) at any ordinary global load's use.
+// __forceinline__ is load-bearing, as for grad_dense_pipe_body.
+template <typename XT, int NW, int DEPTH, int ITERS, typename CoeffOf>
+__device__ __forceinline__ int pipe_drain(
+    const XT* __restrict__ X, long total_elems, int d, const int* rowq,
+    int nq, const float* w_lds, float* gw, int wave, int lane,
+    CoeffOf&& coeff_of) {
+  using RV = RowVec<XT>;
+  typename RV::T buf[DEPTH][ITERS];
+  int n_done = 0;
+  // the counted-wait protocol needs EXACTLY ITERS loads per slot: a
+  // skipped load would let vmcnt(N) pass while this buffer's own loads
+  // are still in flight (vmcnt waits "<= N outstanding", nothing more).
+  // Tail slots load a clamped row instead of skipping.
+  if (nq > 0) {
+#pragma unroll
+    for (int p = 0; p < DEPTH; ++p) {
+      const int q = min(wave + p * NW, nq - 1);
+      const int rr = __builtin_amdgcn_readfirstlane(rowq[q]);
+      const auto rs = row_rsrc<XT>(X, total_elems, rr, d);
+#pragma unroll
+      for (int it = 0; it < ITERS; ++it)
+        buf[p][it] = RV::load(rs, (lane + it * WAVE) << RV::VOFF_SHIFT);
+    }
+  }
+  int q_base = wave;
+  while (q_base < nq) {
+#pragma unroll
+    for (int p = 0; p < DEPTH; ++p) {
+      const int q = q_base + p * NW;
+      if (q < nq) {
+        float z = 0.f;
+#pragma unroll
+        for (int it = 0; it < ITERS; ++it) {
+          float o[4];
+          cvt4(buf[p][it], o);
+          const int j4 = lane + it * WAVE;
+          const float4 wv = reinterpret_cast<const float4*>(w_lds)[j4];
+          z += o[0] * wv.x + o[1] * wv.y + o[2] * wv.z + o[3] * wv.w;
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1)
+          z += __shfl_xor(z, off, WAVE);
+        const float coeff = coeff_of(q, z);
+        ++n_done;
+#pragma unroll
+        for (int it = 0; it < ITERS; ++it) {
+          float o[4];
+          cvt4(buf[p][it], o);
+          const int j4 = lane + it * WAVE;
+          float4* gw4 = reinterpret_cast<float4*>(gw);
+          float4 cur = gw4[j4];
+          cur.x += coeff * o[0]; cur.y += coeff * o[1];
+          cur.z += coeff * o[2]; cur.w += coeff * o[3];
+          gw4[j4] = cur;
+        }
+        // refill this buffer DEPTH rows ahead (clamped: see prologue).
+        // sched_barrier pins every read of buf[p] (the accumulate above)
+        // BEFORE the async refill overwrites it — the compiler treats an
+        // asm load's register write as instantaneous and would otherwise
+        // rotate reads past the issue (observed: regalloc preservation
+        // copies racing the in-flight load).
+        __builtin_amdgcn_sched_barrier(0);
+        const int qf = min(q + DEPTH * NW, nq - 1);
+        {
+          const int rr2 = __builtin_amdgcn_readfirstlane(rowq[qf]);
+          const auto rs2 = row_rsrc<XT>(X, total_elems, rr2, d);
+#pragma unroll
+          for (int it = 0; it < ITERS; ++it)
+            buf[p][it] = RV::load(rs2, (lane + it * WAVE) << RV::VOFF_SHIFT);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    }
+    q_base += DEPTH * NW;
+  }
+  return n_done;
+}
+
+// Slab flush of the graph engine's forms: the block's [NW][DPAD] wave slabs
+// summed into its column of the transposed partials, g_part[j*G + bid]
+// (plain stores; reduce_partials sums the G columns).
+template <int PBLOCK, int NW, int DPAD>
+__device__ __forceinline__ void flush_partials(const float* gacc,
+                                               float* __restrict__ g_part,
+                                               int d, size_t G, int bid) {
+  for (int j = threadIdx.x; j < d; j += PBLOCK) {
+    float s = 0.f;
+#pragma unroll
+    for (int s2 = 0; s2 < NW; ++s2) s += gacc[(size_t)s2 * DPAD + j];
+    g_part[(size_t)j * G + bid] = s;
+  }
+}
+
 // Standalone mask scan: fills a GLOBAL compacted row list (+ prefetched y
 // values) for a FUTURE round. The scan depends only on (seed, round), not on
 // w — so the graph engine runs round r+1's scan on a side stream overlapped
@@ -404,8 +564,7 @@ __device__ void scan_rows_body(
     uint32_t round_k, uint64_t row_start, uint32_t threshold, int take_all,
     int bid, int nblk) {
   if (scan_round_dev) round_k = (uint32_t)(*scan_round_dev);
-  constexpr int SCAP = 2048;
-  __shared__ int rows_s[SCAP];
+  __shared__ int rows_s[QCAP];
   __shared__ int qn_s, base_s;
   if (threadIdx.x == 0) qn_s = 0;
   const int wave = threadIdx.x >> 6;
@@ -414,29 +573,11 @@ __device__ void scan_rows_body(
   long gi = bid;
   bool done = false;
   while (!done) {
-    while (true) {
-      __syncthreads();
-      if (gi >= ngroups || qn_s >= SCAP - ROWS_PER_BLOCK_ITER) break;
-      const long base = gi * (long)ROWS_PER_BLOCK_ITER +
-                        (long)wave * ROWS_PER_WAVE;
-      if (base < n_rows) {
-        const uint4 x = philox_block4(
-            seed, round_k, (row_start + (uint64_t)base) / 4 + (uint64_t)lane);
-        const long rem = n_rows - base;
-        const long lrow = base + 4L * lane;
-        const uint32_t xs[4] = {x.x, x.y, x.z, x.w};
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          if (4L * lane + i < rem && (take_all || xs[i] < threshold)) {
-            const int pos = atomicAdd(&qn_s, 1);
-            rows_s[pos] = (int)(lrow + i);
-          }
-        }
-      }
-      gi += nblk;
-    }
+    scan_enqueue<ROWS_PER_BLOCK_ITER>(rows_s, &qn_s, QCAP, gi, ngroups, nblk,
+                                      n_rows, seed, round_k, row_start,
+                                      threshold, take_all, wave, lane);
     __syncthreads();
-    const int nq = min(qn_s, SCAP);
+    const int nq = min(qn_s, QCAP);
     if (threadIdx.x == 0 && nq > 0) base_s = atomicAdd(count_dev, nq);
     __syncthreads();
     for (int i = threadIdx.x; i < nq; i += BLOCK) {
@@ -472,14 +613,14 @@ __global__ __launch_bounds__(PBLOCK) void grad_dense_list_kernel(
     float* __restrict__ g_part, const int* __restrict__ rowlist,
     const float* __restrict__ ylist, const int* __restrict__ count_dev,
     long n_rows, int d, int objective) {
-  constexpr int NW = PBLOCK / WAVE;
-  constexpr int DPAD = ITERS * 256;
-  constexpr int LCAP = 2048;
+  static_assert(PBLOCK == PIPE_BLOCK, "LDS sizes assume PIPE_BLOCK threads");
+  constexpr int NW = PIPE_NW;
+  constexpr int DPAD = pipe_dpad(ITERS);
   extern __shared__ float smem[];
   float* w_lds = smem;                                // [DPAD]
   float* gacc = smem + DPAD;                          // [NW][DPAD]
-  float* yq = smem + (size_t)(1 + NW) * DPAD;         // [LCAP]
-  int* rowq = (int*)(yq + LCAP);                      // [LCAP]
+  float* yq = smem + (size_t)(1 + NW) * DPAD;         // [QCAP]
+  int* rowq = (int*)(yq + QCAP);                      // [QCAP]
   for (int j = threadIdx.x; j < DPAD; j += PBLOCK) {
     w_lds[j] = j < d ? w[j] : 0.f;
 #pragma unroll
@@ -489,84 +630,24 @@ __global__ __launch_bounds__(PBLOCK) void grad_dense_list_kernel(
   const int lane = threadIdx.x & 63;
   float* gw = gacc + (size_t)wave * DPAD;
   const long total_elems = n_rows * (long)d;
-  using RV = RowVec<XT>;
   const int total = *count_dev;
   const int per_block = (total + gridDim.x - 1) / gridDim.x;
   const int my0 = blockIdx.x * per_block;
   const int my1 = min(total, my0 + per_block);
-  for (int off = my0; off < my1; off += LCAP) {
-    const int nq = min(my1 - off, LCAP);
+  for (int off = my0; off < my1; off += QCAP) {
+    const int nq = min(my1 - off, QCAP);
     __syncthreads();
     for (int i = threadIdx.x; i < nq; i += PBLOCK) {
       rowq[i] = rowlist[off + i];
       yq[i] = ylist[off + i];
     }
     __syncthreads();
-    typename RV::T buf[DEPTH][ITERS];
-    if (nq > 0) {
-#pragma unroll
-      for (int p = 0; p < DEPTH; ++p) {
-        const int q = min(wave + p * NW, nq - 1);
-        const int rr = __builtin_amdgcn_readfirstlane(rowq[q]);
-        const auto rs = row_rsrc<XT>(X, total_elems, rr, d);
-#pragma unroll
-        for (int it = 0; it < ITERS; ++it)
-          buf[p][it] = RV::load(rs, (lane + it * WAVE) << RV::VOFF_SHIFT);
-      }
-    }
-    int q_base = wave;
-    while (q_base < nq) {
-#pragma unroll
-      for (int p = 0; p < DEPTH; ++p) {
-        const int q = q_base + p * NW;
-        if (q < nq) {
-          float z = 0.f;
-#pragma unroll
-          for (int it = 0; it < ITERS; ++it) {
-            float o[4];
-            cvt4(buf[p][it], o);
-            const int j4 = lane + it * WAVE;
-            const float4 wv = reinterpret_cast<const float4*>(w_lds)[j4];
-            z += o[0] * wv.x + o[1] * wv.y + o[2] * wv.z + o[3] * wv.w;
-          }
-#pragma unroll
-          for (int offx = 32; offx > 0; offx >>= 1)
-            z += __shfl_xor(z, offx, WAVE);
-          const float coeff = link_residual(z, yq[q], objective);
-#pragma unroll
-          for (int it = 0; it < ITERS; ++it) {
-            float o[4];
-            cvt4(buf[p][it], o);
-            const int j4 = lane + it * WAVE;
-            float4* gw4 = reinterpret_cast<float4*>(gw);
-            float4 cur = gw4[j4];
-            cur.x += coeff * o[0]; cur.y += coeff * o[1];
-            cur.z += coeff * o[2]; cur.w += coeff * o[3];
-            gw4[j4] = cur;
-          }
-          __builtin_amdgcn_sched_barrier(0);
-          const int qf = min(q + DEPTH * NW, nq - 1);
-          {
-            const int rr2 = __builtin_amdgcn_readfirstlane(rowq[qf]);
-            const auto rs2 = row_rsrc<XT>(X, total_elems, rr2, d);
-#pragma unroll
-            for (int it = 0; it < ITERS; ++it)
-              buf[p][it] = RV::load(rs2, (lane + it * WAVE) << RV::VOFF_SHIFT);
-          }
-          __builtin_amdgcn_sched_barrier(0);
-        }
-      }
-      q_base += DEPTH * NW;
-    }
+    pipe_drain<XT, NW, DEPTH, ITERS>(
+        X, total_elems, d, rowq, nq, w_lds, gw, wave, lane,
+        [&](int q, float z) { return link_residual(z, yq[q], objective); });
   }
   __syncthreads();
-  const size_t G = gridDim.x;
-  for (int j = threadIdx.x; j < d; j += PBLOCK) {
-    float s = 0.f;
-#pragma unroll
-    for (int s2 = 0; s2 < NW; ++s2) s += gacc[(size_t)s2 * DPAD + j];
-    g_part[(size_t)j * G + blockIdx.x] = s;
-  }
+  flush_partials<PBLOCK, NW, DPAD>(gacc, g_part, d, gridDim.x, blockIdx.x);
 }
 
 // __forceinline__ is load-bearing: left out of line, the body inherits no
@@ -584,9 +665,10 @@ __device__ __forceinline__ void grad_dense_pipe_body(
     unsigned long long done_val, unsigned long long* done_arr, int bid,
     int nblk) {
   if (k_dev) round_k = (uint32_t)(*k_dev) + 1u;
-  constexpr int NW = PBLOCK / WAVE;
+  static_assert(PBLOCK == PIPE_BLOCK, "LDS sizes assume PIPE_BLOCK threads");
+  constexpr int NW = PIPE_NW;
   constexpr int RPB = NW * ROWS_PER_WAVE;
-  constexpr int DPAD = ITERS * 256;  // padded feature dim
+  constexpr int DPAD = pipe_dpad(ITERS);  // padded feature dim
   static_assert(QCAP >= RPB + 1024, "queue must out-size one scan iter");
   extern __shared__ float smem[];
   float* w_lds = smem;                               // [DPAD]
@@ -608,35 +690,14 @@ __device__ __forceinline__ void grad_dense_pipe_body(
   float* gw = gacc + (size_t)wave * DPAD;
   int local_count = 0;
   const long total_elems = n_rows * (long)d;
-  using RV = RowVec<XT>;
 
   const long ngroups = (n_rows + RPB - 1) / RPB;
   long gi = bid;
   bool done = false;
   while (!done) {
-    // ---- scan phase: enqueues row ids only (a y[row] load per hit would
-    // expose one global-load latency per scan iteration ahead of the
-    // iteration's barrier)
-    while (true) {
-      __syncthreads();
-      if (gi >= ngroups || *qn >= QCAP - RPB) break;
-      const long base = gi * (long)RPB + (long)wave * ROWS_PER_WAVE;
-      if (base < n_rows) {
-        const uint4 x = philox_block4(
-            seed, round_k, (row_start + (uint64_t)base) / 4 + (uint64_t)lane);
-        const long rem = n_rows - base;
-        const long lrow = base + 4L * lane;
-        const uint32_t xs[4] = {x.x, x.y, x.z, x.w};
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          if (4L * lane + i < rem && (take_all || xs[i] < threshold)) {
-            const int pos = atomicAdd(qn, 1);
-            rowq[pos] = (int)(lrow + i);
-          }
-        }
-      }
-      gi += nblk;
-    }
+    // ---- scan phase
+    scan_enqueue<RPB>(rowq, qn, QCAP, gi, ngroups, nblk, n_rows, seed,
+                      round_k, row_start, threshold, take_all, wave, lane);
     __syncthreads();
     const int nq = min(*qn, QCAP);
     // ---- fetch phase: y (and the SAGA history scalar) for the whole queue
@@ -647,79 +708,16 @@ __device__ __forceinline__ void grad_dense_pipe_body(
       if (SAGA) aq[pos] = alpha[row];
     }
     __syncthreads();
-    // ---- process phase: DEPTH-deep static pipeline, buffer loads only
-    typename RV::T buf[DEPTH][ITERS];
-    // the counted-wait protocol needs EXACTLY ITERS loads per slot: a
-    // skipped load would let vmcnt(N) pass while this buffer's own loads
-    // are still in flight (vmcnt waits "<= N outstanding", nothing more).
-    // Tail slots load a clamped row instead of skipping.
-    if (nq > 0) {
-#pragma unroll
-      for (int p = 0; p < DEPTH; ++p) {
-        const int q = min(wave + p * NW, nq - 1);
-        const int rr = __builtin_amdgcn_readfirstlane(rowq[q]);
-        const auto rs = row_rsrc<XT>(X, total_elems, rr, d);
-#pragma unroll
-        for (int it = 0; it < ITERS; ++it)
-          buf[p][it] = RV::load(rs, (lane + it * WAVE) << RV::VOFF_SHIFT);
-      }
-    }
-    int q_base = wave;
-    while (q_base < nq) {
-#pragma unroll
-      for (int p = 0; p < DEPTH; ++p) {
-        const int q = q_base + p * NW;
-        if (q < nq) {
-          float z = 0.f;
-#pragma unroll
-          for (int it = 0; it < ITERS; ++it) {
-            float o[4];
-            cvt4(buf[p][it], o);
-            const int j4 = lane + it * WAVE;
-            const float4 wv = reinterpret_cast<const float4*>(w_lds)[j4];
-            z += o[0] * wv.x + o[1] * wv.y + o[2] * wv.z + o[3] * wv.w;
-          }
-#pragma unroll
-          for (int off = 32; off > 0; off >>= 1)
-            z += __shfl_xor(z, off, WAVE);
-          float e = link_residual(z, yq[q], objective);
-          float coeff = e;
-          if (SAGA) {
-            coeff = e - aq[q];
-            if (lane == 0) eq[q] = e;  // committed after the barrier
-          }
-          ++local_count;
-#pragma unroll
-          for (int it = 0; it < ITERS; ++it) {
-            float o[4];
-            cvt4(buf[p][it], o);
-            const int j4 = lane + it * WAVE;
-            float4* gw4 = reinterpret_cast<float4*>(gw);
-            float4 cur = gw4[j4];
-            cur.x += coeff * o[0]; cur.y += coeff * o[1];
-            cur.z += coeff * o[2]; cur.w += coeff * o[3];
-            gw4[j4] = cur;
-          }
-          // refill this buffer DEPTH rows ahead (clamped: see prologue).
-          // sched_barrier pins every read of buf[p] (the accumulate above)
-          // BEFORE the async refill overwrites it — the compiler treats an
-          // asm load's register write as instantaneous and would otherwise
-          // rotate reads past the issue (observed: regalloc preservation
-          // copies racing the in-flight load).
-          __builtin_amdgcn_sched_barrier(0);
-          const int qf = min(q + DEPTH * NW, nq - 1);
-          {
-            const int rr2 = __builtin_amdgcn_readfirstlane(rowq[qf]);
-            const auto rs2 = row_rsrc<XT>(X, total_elems, rr2, d);
-#pragma unroll
-            for (int it = 0; it < ITERS; ++it)
-              buf[p][it] = RV::load(rs2, (lane + it * WAVE) << RV::VOFF_SHIFT);
-          }
-          __builtin_amdgcn_sched_barrier(0);
-        }
-      }
-      q_base += DEPTH * NW;
-    }
+    // ---- process phase
+    local_count += pipe_drain<XT, NW, DEPTH, ITERS>(
+        X, total_elems, d, rowq, nq, w_lds, gw, wave, lane,
+        [&](int q, float z) {
+          const float e = link_residual(z, yq[q], objective);
+          if (!SAGA) return e;
+          const float coeff = e - aq[q];
+          if (lane == 0) eq[q] = e;  // committed after the barrier
+          return coeff;
+        });
     __syncthreads();
     if (SAGA) {
       // history scalar emit/commit, batched outside the pipeline
@@ -744,13 +742,7 @@ __device__ __forceinline__ void grad_dense_pipe_body(
   }
   __syncthreads();
   if (g_part != nullptr) {
-    const size_t G = nblk;
-    for (int j = threadIdx.x; j < d; j += PBLOCK) {
-      float s = 0.f;
-#pragma unroll
-      for (int s2 = 0; s2 < NW; ++s2) s += gacc[(size_t)s2 * DPAD + j];
-      g_part[(size_t)j * G + bid] = s;
-    }
+    flush_partials<PBLOCK, NW, DPAD>(gacc, g_part, d, nblk, bid);
   } else {
     for (int j = threadIdx.x; j < d; j += PBLOCK) {
       float s = 0.f;
@@ -1045,39 +1037,17 @@ __global__ void alpha_gather_wave_kernel(
 }
 
 
-// ------------------------------------------------- elastic-net step (REG)
-// The REG=true forms of the update kernels minimise
-//   F(w) = (1/N) sum_i f_i(w) + (l2/2)|w|^2 + l1*|w|_1
-// with one step per applied update, on the value already in a register:
-//   v = w - eta*(ghat + l2*w)                  L2: exact gradient step
-//   w = v > t ? v - t : (v < -t ? v + t : +0)  L1: prox, t = eta*l1
-// written as v = fma(-step, g, dec*w) with dec = fma(-eta, l2, 1) — for
-// l1 = 0 literally MLlib's SquaredL2Updater w*(1 - eta*l2) - eta*ghat, for
-// l2 = 0 its L1Updater. Every product and sum below is an explicit
-// single-rounding intrinsic, so the rounding count the tests assume does
-// not depend on the contraction mode. No extra global load or store: the
-// REG=false instantiations keep the old bodies and the old bits.
-__device__ __forceinline__ float reg_dec(float eta, float l2) {
-  return fmaf(-eta, l2, 1.f);
-}
-__device__ __forceinline__ float reg_thr(float eta, float l1) {
-  return __fmul_rn(eta, l1);
-}
-// |v| - t is computed unconditionally and its sign decides (v - t for
-// v > t and v + t for v < -t are +-(|v| - t) with the same single rounding;
-// anything else, a NaN included, is +0): two selects, no divergent branch —
-// the nested-ternary form compiled to an exec-mask branch per element.
-__device__ __forceinline__ float reg_prox(float v, float t) {
-  const float a = __fsub_rn(fabsf(v), t);
-  return a > 0.f ? copysignf(a, v) : 0.f;
-}
-// v for a step whose data term is step*g
-__device__ __forceinline__ float reg_step(float w, float g, float step,
-                                          float dec, float t) {
-  return reg_prox(fmaf(-step, g, __fmul_rn(dec, w)), t);
-}
-
 // ---------------------------------------------------------------- K5/K6
+// Every kernel below applies asgd_step / saga_step of update_step.h (the
+// arithmetic, plain and elastic-net, is defined and explained there) to a
+// value it holds in a register: no REG form adds a global load or store.
+
+// the REG scale is an explicit single rounding, like the rest of that step
+template <bool REG>
+__device__ __forceinline__ float step_scale(float gamma_k, float inv_batch) {
+  if constexpr (REG) return __fmul_rn(gamma_k, inv_batch);
+  else return gamma_k * inv_batch;
+}
 
 template <bool REG>
 __global__ void sgd_update_kernel(float* __restrict__ w,
@@ -1085,20 +1055,11 @@ __global__ void sgd_update_kernel(float* __restrict__ w,
                                   float inv_batch, int d, float l2,
                                   float l1) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if constexpr (REG) {
-    if (i < d)
-      w[i] = reg_step(w[i], g[i], __fmul_rn(gamma_k, inv_batch),
-                      reg_dec(gamma_k, l2), reg_thr(gamma_k, l1));
-  } else {
-    if (i < d) w[i] -= gamma_k * inv_batch * g[i];
-  }
+  if (i < d)
+    asgd_step<REG>(w[i], g[i], step_scale<REG>(gamma_k, inv_batch),
+                   reg_dec(gamma_k, l2), reg_thr(gamma_k, l1));
 }
 
-// w -= gamma*(inv_batch*g + alpha_bar_old); alpha_bar += inv_N*g
-// (order matches reference SparkASAGASync.scala:300-304 /
-//  SparkASAGAThread.scala:217-220: w reads the OLD alpha_bar).
-// REG: prox-SAGA — ghat = inv_batch*g + alpha_bar_old, eta = gamma; the
-// penalty stays out of alpha_bar (and out of the history table).
 template <bool REG>
 __global__ void saga_update_kernel(float* __restrict__ w,
                                    const float* __restrict__ g,
@@ -1106,48 +1067,9 @@ __global__ void saga_update_kernel(float* __restrict__ w,
                                    float inv_batch, float inv_N, int d,
                                    float l2, float l1) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if constexpr (REG) {
-    if (i < d) {
-      const float gi = g[i];
-      const float ab = alpha_bar[i];
-      w[i] = reg_step(w[i], fmaf(inv_batch, gi, ab), gamma,
-                      reg_dec(gamma, l2), reg_thr(gamma, l1));
-      alpha_bar[i] = fmaf(inv_N, gi, ab);
-    }
-  } else {
-    if (i < d) {
-      const float gi = g[i];
-      w[i] -= gamma * (inv_batch * gi + alpha_bar[i]);
-      alpha_bar[i] += inv_N * gi;
-    }
-  }
-}
-
-// update + gradient-buffer zeroing fused (native engine: saves one
-// fillBuffer launch per accepted round; rejected rounds re-zero g at the
-// next dispatch instead)
-__global__ void sgd_update_zero_kernel(float* __restrict__ w,
-                                       float* __restrict__ g, float gamma_k,
-                                       float inv_batch, int d) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < d) {
-    w[i] -= gamma_k * inv_batch * g[i];
-    g[i] = 0.f;
-  }
-}
-
-__global__ void saga_update_zero_kernel(float* __restrict__ w,
-                                        float* __restrict__ g,
-                                        float* __restrict__ alpha_bar,
-                                        float gamma, float inv_batch,
-                                        float inv_N, int d) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < d) {
-    const float gi = g[i];
-    w[i] -= gamma * (inv_batch * gi + alpha_bar[i]);
-    alpha_bar[i] += inv_N * gi;
-    g[i] = 0.f;
-  }
+  if (i < d)
+    saga_step<REG>(w[i], alpha_bar[i], g[i], gamma, inv_batch, inv_N,
+                   reg_dec(gamma, l2), reg_thr(gamma, l1));
 }
 
 __global__ void saga_commit_kernel(float* __restrict__ alpha,
@@ -1215,24 +1137,7 @@ __global__ void saga_commit_devn_kernel(float* __restrict__ alpha,
 #define MU_BLOCK 64
 #define MU_CHUNK 8
 
-__device__ __forceinline__ void mu_asgd(float& w, float g, float scale) {
-  w -= scale * g;
-}
-__device__ __forceinline__ void mu_saga(float& w, float& ab, float g,
-                                        float gamma, float inv_batch,
-                                        float inv_N) {
-  w -= gamma * (inv_batch * g + ab);
-  ab += inv_N * g;
-}
-// regularised forms (REG): one decay-and-threshold step per gradient
-__device__ __forceinline__ void mu_saga_reg(float& w, float& ab, float g,
-                                            float gamma, float inv_batch,
-                                            float inv_N, float dec, float t) {
-  w = reg_step(w, fmaf(inv_batch, g, ab), gamma, dec, t);
-  ab = fmaf(inv_N, g, ab);
-}
-
-// REG applies the elastic-net step (above) once per accepted gradient, in
+// REG applies the elastic-net step once per accepted gradient, in
 // batch order — n gradients are n decay-and-threshold steps, the same as n
 // singleton launches — with eta = a.eta[j] (ASGD) or gamma (ASAGA). Only
 // the apply stage's arithmetic differs: same global loads, same stores, so
@@ -1273,45 +1178,21 @@ __global__ __launch_bounds__(MU_BLOCK) void multi_update_kernel(
       for (int c = 0; c < MU_CHUNK; ++c) {
         const int j = j0 + c;
         if (j < a.n) {
+          float dec = 1.f, t = 0.f;
           if constexpr (REG) {
             const float eta = a.algo == 0 ? eta_c[c] : gamma;
-            const float dec = reg_dec(eta, l2), t = reg_thr(eta, l1);
-            if constexpr (VEC4) {
-              if (a.algo == 0) {
-                const float sc = sc_c[c];
-                wi.x = reg_step(wi.x, gv[c].x, sc, dec, t);
-                wi.y = reg_step(wi.y, gv[c].y, sc, dec, t);
-                wi.z = reg_step(wi.z, gv[c].z, sc, dec, t);
-                wi.w = reg_step(wi.w, gv[c].w, sc, dec, t);
-              } else {
-                mu_saga_reg(wi.x, ab.x, gv[c].x, gamma, inv_batch, inv_N,
-                            dec, t);
-                mu_saga_reg(wi.y, ab.y, gv[c].y, gamma, inv_batch, inv_N,
-                            dec, t);
-                mu_saga_reg(wi.z, ab.z, gv[c].z, gamma, inv_batch, inv_N,
-                            dec, t);
-                mu_saga_reg(wi.w, ab.w, gv[c].w, gamma, inv_batch, inv_N,
-                            dec, t);
-              }
-            } else {
-              if (a.algo == 0) wi = reg_step(wi, gv[c], sc_c[c], dec, t);
-              else mu_saga_reg(wi, ab, gv[c], gamma, inv_batch, inv_N, dec,
-                               t);
-            }
-          } else if constexpr (VEC4) {
-            if (a.algo == 0) {
-              const float sc = a.scale[j];
-              mu_asgd(wi.x, gv[c].x, sc); mu_asgd(wi.y, gv[c].y, sc);
-              mu_asgd(wi.z, gv[c].z, sc); mu_asgd(wi.w, gv[c].w, sc);
-            } else {
-              mu_saga(wi.x, ab.x, gv[c].x, gamma, inv_batch, inv_N);
-              mu_saga(wi.y, ab.y, gv[c].y, gamma, inv_batch, inv_N);
-              mu_saga(wi.z, ab.z, gv[c].z, gamma, inv_batch, inv_N);
-              mu_saga(wi.w, ab.w, gv[c].w, gamma, inv_batch, inv_N);
-            }
+            dec = reg_dec(eta, l2);
+            t = reg_thr(eta, l1);
+          }
+          if (a.algo == 0) {
+            const float sc = REG ? sc_c[c] : a.scale[j];
+            for_lanes([&](float& w1, float g1) {
+              asgd_step<REG>(w1, g1, sc, dec, t);
+            }, wi, gv[c]);
           } else {
-            if (a.algo == 0) mu_asgd(wi, gv[c], a.scale[j]);
-            else mu_saga(wi, ab, gv[c], gamma, inv_batch, inv_N);
+            for_lanes([&](float& w1, float& ab1, float g1) {
+              saga_step<REG>(w1, ab1, g1, gamma, inv_batch, inv_N, dec, t);
+            }, wi, ab, gv[c]);
           }
         }
       }
@@ -1339,7 +1220,7 @@ __global__ __launch_bounds__(MU_BLOCK) void multi_update_kernel(
 //   mode 2 mllib: w -= scale * s / max(n,1) (scale = gamma_k, host;
 //                 n = sum_p ctr_p[0], the round's ACTUAL sample count, read
 //                 here on the device — no D2H);
-//   REG: the same step with the elastic-net terms (helpers above), once
+//   REG: the same step with the elastic-net terms (update_step.h), once
 //                 per round: v = dec*w - step*s (asgd/mllib, step = the
 //                 scale above) or dec*w - gamma*(inv_batch*s + alpha_bar)
 //                 (asaga), then the soft-threshold. ``eta`` is the bare
@@ -1375,75 +1256,31 @@ __global__ __launch_bounds__(SRU_BLOCK) void sync_round_update_kernel(
   }
   [[maybe_unused]] const float dec = REG ? reg_dec(eta, l2) : 1.f;
   [[maybe_unused]] const float thr = REG ? reg_thr(eta, l1) : 0.f;
+  using V = typename std::conditional<VEC4, float4, float>::type;
+  const int nel = VEC4 ? d >> 2 : d;
   const int stride = gridDim.x * SRU_BLOCK;
-  if (VEC4) {
-    const int n4 = d >> 2;
-    for (int i = blockIdx.x * SRU_BLOCK + threadIdx.x; i < n4; i += stride) {
-      float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (int i = blockIdx.x * SRU_BLOCK + threadIdx.x; i < nel; i += stride) {
+    V s = V{};
 #pragma unroll 8
-      for (int p = 0; p < P; ++p) {
-        const float4 v = reinterpret_cast<const float4*>(g_tab[p])[i];
-        s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
-      }
-      for (int p = 0; p < P; ++p)
-        reinterpret_cast<float4*>(g_tab[p])[i] =
-            make_float4(0.f, 0.f, 0.f, 0.f);
-      float4 wi = reinterpret_cast<float4*>(w)[i];
-      if constexpr (REG) {
-        if (mode == 1) {
-          float4 ab = reinterpret_cast<float4*>(alpha_bar)[i];
-          mu_saga_reg(wi.x, ab.x, s.x, gamma, inv_batch, inv_N, dec, thr);
-          mu_saga_reg(wi.y, ab.y, s.y, gamma, inv_batch, inv_N, dec, thr);
-          mu_saga_reg(wi.z, ab.z, s.z, gamma, inv_batch, inv_N, dec, thr);
-          mu_saga_reg(wi.w, ab.w, s.w, gamma, inv_batch, inv_N, dec, thr);
-          reinterpret_cast<float4*>(alpha_bar)[i] = ab;
-        } else {
-          wi.x = reg_step(wi.x, s.x, scale, dec, thr);
-          wi.y = reg_step(wi.y, s.y, scale, dec, thr);
-          wi.z = reg_step(wi.z, s.z, scale, dec, thr);
-          wi.w = reg_step(wi.w, s.w, scale, dec, thr);
-        }
-      } else if (mode == 1) {
-        float4 ab = reinterpret_cast<float4*>(alpha_bar)[i];
-        wi.x -= gamma * (inv_batch * s.x + ab.x);
-        wi.y -= gamma * (inv_batch * s.y + ab.y);
-        wi.z -= gamma * (inv_batch * s.z + ab.z);
-        wi.w -= gamma * (inv_batch * s.w + ab.w);
-        ab.x += inv_N * s.x; ab.y += inv_N * s.y;
-        ab.z += inv_N * s.z; ab.w += inv_N * s.w;
-        reinterpret_cast<float4*>(alpha_bar)[i] = ab;
-      } else {
-        wi.x -= scale * s.x; wi.y -= scale * s.y;
-        wi.z -= scale * s.z; wi.w -= scale * s.w;
-      }
-      reinterpret_cast<float4*>(w)[i] = wi;
-      if (snap_dst) reinterpret_cast<float4*>(snap_dst)[i] = wi;
+    for (int p = 0; p < P; ++p) {
+      const V v = reinterpret_cast<const V*>(g_tab[p])[i];
+      for_lanes([](float& s1, float v1) { s1 += v1; }, s, v);
     }
-  } else {
-    for (int i = blockIdx.x * SRU_BLOCK + threadIdx.x; i < d; i += stride) {
-      float s = 0.f;
-#pragma unroll 8
-      for (int p = 0; p < P; ++p) s += g_tab[p][i];
-      for (int p = 0; p < P; ++p) g_tab[p][i] = 0.f;
-      float wi = w[i];
-      if constexpr (REG) {
-        if (mode == 1) {
-          float ab = alpha_bar[i];
-          mu_saga_reg(wi, ab, s, gamma, inv_batch, inv_N, dec, thr);
-          alpha_bar[i] = ab;
-        } else {
-          wi = reg_step(wi, s, scale, dec, thr);
-        }
-      } else if (mode == 1) {
-        const float ab = alpha_bar[i];
-        wi -= gamma * (inv_batch * s + ab);
-        alpha_bar[i] = ab + inv_N * s;
-      } else {
-        wi -= scale * s;
-      }
-      w[i] = wi;
-      if (snap_dst) snap_dst[i] = wi;
+    for (int p = 0; p < P; ++p) reinterpret_cast<V*>(g_tab[p])[i] = V{};
+    V wi = reinterpret_cast<V*>(w)[i];
+    if (mode == 1) {
+      V ab = reinterpret_cast<V*>(alpha_bar)[i];
+      for_lanes([&](float& w1, float& ab1, float s1) {
+        saga_step<REG>(w1, ab1, s1, gamma, inv_batch, inv_N, dec, thr);
+      }, wi, ab, s);
+      reinterpret_cast<V*>(alpha_bar)[i] = ab;
+    } else {
+      for_lanes([&](float& w1, float s1) {
+        asgd_step<REG>(w1, s1, scale, dec, thr);
+      }, wi, s);
     }
+    reinterpret_cast<V*>(w)[i] = wi;
+    if (snap_dst) reinterpret_cast<V*>(snap_dst)[i] = wi;
   }
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -1489,7 +1326,7 @@ __global__ __launch_bounds__(BLOCK) void sgd_reduce_update_kernel(
       for (int b = b0; b < b1; ++b) s += base[b];
     }
     if (splits == 1) {
-      w[j] -= gamma_k * inv_batch * s;
+      asgd_step<false>(w[j], s, gamma_k * inv_batch);
     } else {
       atomicAdd(&w[j], -gamma_k * inv_batch * s);
     }
@@ -1518,7 +1355,7 @@ __global__ __launch_bounds__(1024) void sgd_update_fused_kernel(
   const float gamma_k =
       (float)((double)gamma / sqrt((double)(k / num_part + 1)));
   for (int i = threadIdx.x; i < d; i += blockDim.x) {
-    w[i] -= gamma_k * inv_batch * g[i];
+    asgd_step<false>(w[i], g[i], gamma_k * inv_batch);
     g[i] = 0.f;
   }
   __syncthreads();
@@ -1530,9 +1367,7 @@ __global__ __launch_bounds__(1024) void saga_update_fused_kernel(
     float* __restrict__ alpha_bar, int* __restrict__ k_dev, float gamma,
     float inv_batch, float inv_N, int d) {
   for (int i = threadIdx.x; i < d; i += blockDim.x) {
-    const float gi = g[i];
-    w[i] -= gamma * (inv_batch * gi + alpha_bar[i]);
-    alpha_bar[i] += inv_N * gi;
+    saga_step<false>(w[i], alpha_bar[i], g[i], gamma, inv_batch, inv_N);
     g[i] = 0.f;
   }
   __syncthreads();
@@ -1564,8 +1399,8 @@ static inline int pick_lpr(int d) {
 // Pipelined-kernel template parameters for a feature dim (callers guarantee
 // d % 4 == 0 and d <= 2048). Depth: measured on the wave kernel, 6 wins at
 // ITERS <= 4 and 4 at the wider fp32 shapes (profiles/r04_grad_occupancy.md);
-// solo launches keep 4. ASYNCAMD_PIPE_DEPTH overrides (1, 2, 4, 6 or 8; any
-// other value runs as 4).
+// solo and list launches keep 4. ASYNCAMD_PIPE_DEPTH overrides (1, 2, 4, 6
+// or 8; any other value runs as 4) for the pipe, wave and list kernels.
 static inline int pipe_iters(int d) {
   const int it = (d + 255) / 256;
   return it < 1 ? 1 : (it > 8 ? 8 : it);
@@ -1576,73 +1411,121 @@ static inline int pipe_depth(int iters, bool wave) {
   return (depth == 1 || depth == 2 || depth == 6 || depth == 8) ? depth : 4;
 }
 
-// Calls f(integral_constant<ITERS>, integral_constant<DEPTH>) for the
-// runtime (iters, depth) pair: the one switch over the instantiated shapes.
+// ---- runtime value -> template argument. Every launcher picks its
+// instantiation through these three; there are no launch macros.
+//
+// f(integral_constant<int, V>) for the candidate V equal to v — the LAST
+// candidate when none is (so the last one is the default).
+template <int V0, int... Vs, typename F>
+static void with_const(int v, F&& f) {
+  if constexpr (sizeof...(Vs) == 0) f(std::integral_constant<int, V0>{});
+  else if (v == V0) f(std::integral_constant<int, V0>{});
+  else with_const<Vs...>(v, f);
+}
+// f(bool_constant<b>) for a runtime flag
 template <typename F>
-static void with_pipe_shape(int iters, int depth, F&& f) {
-  auto with_depth = [&](auto IT) {
-    switch (depth) {
-      case 1: f(IT, std::integral_constant<int, 1>{}); break;
-      case 2: f(IT, std::integral_constant<int, 2>{}); break;
-      case 6: f(IT, std::integral_constant<int, 6>{}); break;
-      case 8: f(IT, std::integral_constant<int, 8>{}); break;
-      default: f(IT, std::integral_constant<int, 4>{}); break;
-    }
-  };
-  switch (iters) {
-    case 1: with_depth(std::integral_constant<int, 1>{}); break;
-    case 2: with_depth(std::integral_constant<int, 2>{}); break;
-    case 3: with_depth(std::integral_constant<int, 3>{}); break;
-    case 4: with_depth(std::integral_constant<int, 4>{}); break;
-    case 5: with_depth(std::integral_constant<int, 5>{}); break;
-    case 6: with_depth(std::integral_constant<int, 6>{}); break;
-    case 7: with_depth(std::integral_constant<int, 7>{}); break;
-    default: with_depth(std::integral_constant<int, 8>{}); break;
-  }
+static void with_bool(bool b, F&& f) {
+  if (b) f(std::true_type{});
+  else f(std::false_type{});
+}
+// f(element-type tag value, bool_constant<saga>) for a data matrix's runtime
+// (is_bf16, saga) pair; the element type is decltype of the first argument
+template <typename F>
+static void with_xt_saga(int is_bf16, int saga, F&& f) {
+  with_bool(saga != 0, [&](auto SG) {
+    if (is_bf16) f(__hip_bfloat16{}, SG);
+    else f(float{}, SG);
+  });
 }
 
-template <typename XT, bool SAGA>
-static void launch_dense(const XT* X, const float* y, const float* w,
+// f(integral_constant<ITERS>, integral_constant<DEPTH>) for the runtime
+// (iters, depth) pair: the one switch over the instantiated shapes.
+template <typename F>
+static void with_pipe_shape(int iters, int depth, F&& f) {
+  with_const<1, 2, 3, 4, 5, 6, 7, 8>(iters, [&](auto IT) {
+    with_const<1, 2, 6, 8, 4>(depth, [&](auto DP) { f(IT, DP); });
+  });
+}
+
+static inline int csr_lpr() {
+  const char* s = std::getenv("ASYNCAMD_CSR_LPR");
+  const int v = s ? std::atoi(s) : 32;  // measured best on rcv1 shape
+  return (v == 8 || v == 16 || v == 32 || v == 64) ? v : 32;
+}
+
+// The one dense launch: the four extern "C" entry points below differ only
+// in which arguments they leave null.
+static void launch_dense(const void* X, const float* y, const float* w,
                          float* g_out, float* g_part, int* n_out,
                          float* alpha, int* idx_out, float* e_out,
                          int* pos_ctr, const int* k_dev, int commit_now,
                          long n_rows, int d, uint64_t seed, uint32_t round_k,
                          uint64_t row_start, double rate, int objective,
-                         hipStream_t stream,
-                         unsigned long long* done_flag = nullptr,
-                         unsigned long long done_val = 0,
-                         unsigned long long* done_arr = nullptr) {
+                         int x_is_bf16, int saga, hipStream_t stream,
+                         unsigned long long* done_flag,
+                         unsigned long long done_val,
+                         unsigned long long* done_arr) {
   const uint32_t thr = philox_threshold(rate);
   const int take_all = rate >= 1.0;
   const int grid = grad_grid(n_rows);
   const char* np = std::getenv("ASYNCAMD_NO_PIPE");
   const bool pipe_ok = (d % 4 == 0) && (d <= 2048) && !(np && np[0] == '1');
-  if (pipe_ok) {
-    with_pipe_shape(pipe_iters(d), pipe_depth(pipe_iters(d), false),
-                    [&](auto IT, auto DP) {
-      constexpr int it = decltype(IT)::value, dp = decltype(DP)::value;
-      hipLaunchKernelGGL((grad_dense_pipe_kernel<XT, SAGA, 256, dp, it>),
-                         dim3(grid), dim3(256),
-                         (PipeShape<XT, SAGA, dp, it>::LDS), stream, X, y, w,
-                         g_out, g_part, n_out, alpha, idx_out, e_out,
-                         pos_ctr, k_dev, commit_now, n_rows, d, seed,
-                         round_k, row_start, thr, take_all, objective,
-                         done_flag, done_val, done_arr);
+  with_xt_saga(x_is_bf16, saga, [&](auto xt, auto sg) {
+    using XT = decltype(xt);
+    constexpr bool SG = decltype(sg)::value;
+    if (pipe_ok) {
+      const int iters = pipe_iters(d);
+      with_pipe_shape(iters, pipe_depth(iters, false), [&](auto IT, auto DP) {
+        constexpr int it = decltype(IT)::value, dp = decltype(DP)::value;
+        hipLaunchKernelGGL((grad_dense_pipe_kernel<XT, SG, 256, dp, it>),
+                           dim3(grid), dim3(256),
+                           (PipeShape<XT, SG, dp, it>::LDS), stream,
+                           (const XT*)X, y, w, g_out, g_part, n_out, alpha,
+                           idx_out, e_out, pos_ctr, k_dev, commit_now,
+                           n_rows, d, seed, round_k, row_start, thr,
+                           take_all, objective, done_flag, done_val,
+                           done_arr);
+      });
+      return;
+    }
+    const int lpr = pick_lpr(d);
+    const size_t smem = (size_t)(1 + 4 * (WAVE / lpr)) * d * sizeof(float);
+    with_const<16, 32, 64>(lpr, [&](auto L) {
+      hipLaunchKernelGGL((grad_dense_kernel<XT, SG, decltype(L)::value>),
+                         dim3(grid), dim3(BLOCK), smem, stream, (const XT*)X,
+                         y, w, g_out, g_part, n_out, alpha, idx_out, e_out,
+                         pos_ctr, k_dev, commit_now, n_rows, d, seed, round_k,
+                         row_start, thr, take_all, objective, done_flag,
+                         done_val, done_arr);
     });
-    return;
-  }
-  const int lpr = pick_lpr(d);
-  const size_t smem = (size_t)(1 + 4 * (WAVE / lpr)) * d * sizeof(float);
-#define DISPATCH_LPR(L)                                                      \
-  hipLaunchKernelGGL((grad_dense_kernel<XT, SAGA, L>), dim3(grid),           \
-                     dim3(BLOCK), smem, stream, X, y, w, g_out, g_part,      \
-                     n_out, alpha, idx_out, e_out, pos_ctr, k_dev,           \
-                     commit_now, n_rows, d, seed, round_k, row_start, thr,   \
-                     take_all, objective, done_flag, done_val, done_arr)
-  if (lpr == 16) DISPATCH_LPR(16);
-  else if (lpr == 32) DISPATCH_LPR(32);
-  else DISPATCH_LPR(64);
-#undef DISPATCH_LPR
+  });
+}
+
+// The one CSR launch, as launch_dense.
+static void launch_csr(const int* indptr, const int* indices,
+                       const void* values, const float* y, const float* w,
+                       float* alpha, float* g_out, int* n_out, int* idx_out,
+                       float* e_out, int* pos_ctr, const int* k_dev,
+                       int commit_now, long n_rows, uint64_t seed,
+                       uint32_t round_k, uint64_t row_start, double rate,
+                       int objective, int v_is_bf16, int saga,
+                       hipStream_t stream, unsigned long long* done_flag,
+                       unsigned long long done_val,
+                       unsigned long long* done_arr) {
+  const uint32_t thr = philox_threshold(rate);
+  const int take_all = rate >= 1.0;
+  const int grid = grad_grid(n_rows);
+  with_xt_saga(v_is_bf16, saga, [&](auto vt, auto sg) {
+    using VT = decltype(vt);
+    with_const<8, 32, 64, 16>(csr_lpr(), [&](auto L) {
+      hipLaunchKernelGGL(
+          (grad_csr_kernel<VT, decltype(sg)::value, decltype(L)::value>),
+          dim3(grid), dim3(BLOCK), 0, stream, indptr, indices,
+          (const VT*)values, y, w, g_out, n_out, alpha, idx_out, e_out,
+          pos_ctr, k_dev, commit_now, n_rows, seed, round_k, row_start, thr,
+          take_all, objective, done_flag, done_val, done_arr);
+    });
+  });
 }
 
 extern "C" {
@@ -1671,40 +1554,45 @@ void launch_grad_dense_list(const void* X, const float* w, float* g_part,
                             int objective, int x_is_bf16,
                             hipStream_t stream) {
   const int grid = grad_grid(n_rows);
-  const int iters = (d + 255) / 256;
-  const char* dps = std::getenv("ASYNCAMD_PIPE_DEPTH");
-  const int depth = dps ? std::atoi(dps) : 4;
-  const size_t smem = (size_t)5 * (iters * 256) * sizeof(float) +
-                      2048 * (sizeof(float) + sizeof(int));
-#define LIST_LAUNCH_D(XT, CAST, IT, DP)                                      \
-  hipLaunchKernelGGL((grad_dense_list_kernel<XT, 256, DP, IT>), dim3(grid),  \
-                     dim3(256), smem, stream, (CAST)X, w, g_part, rowlist,   \
-                     ylist, count_dev, n_rows, d, objective)
-#define LIST_LAUNCH(XT, CAST, IT)                                            \
-  do {                                                                       \
-    if (depth == 2) LIST_LAUNCH_D(XT, CAST, IT, 2);                          \
-    else if (depth == 6) LIST_LAUNCH_D(XT, CAST, IT, 6);                     \
-    else if (depth == 8) LIST_LAUNCH_D(XT, CAST, IT, 8);                     \
-    else LIST_LAUNCH_D(XT, CAST, IT, 4);                                     \
-  } while (0)
-#define LIST_DISPATCH(XT, CAST)                                              \
-  do {                                                                       \
-    switch (iters) {                                                         \
-      case 1: LIST_LAUNCH(XT, CAST, 1); break;                               \
-      case 2: LIST_LAUNCH(XT, CAST, 2); break;                               \
-      case 3: LIST_LAUNCH(XT, CAST, 3); break;                               \
-      case 4: LIST_LAUNCH(XT, CAST, 4); break;                               \
-      case 5: LIST_LAUNCH(XT, CAST, 5); break;                               \
-      case 6: LIST_LAUNCH(XT, CAST, 6); break;                               \
-      case 7: LIST_LAUNCH(XT, CAST, 7); break;                               \
-      default: LIST_LAUNCH(XT, CAST, 8); break;                              \
-    }                                                                        \
-  } while (0)
-  if (x_is_bf16) LIST_DISPATCH(__hip_bfloat16, const __hip_bfloat16*);
-  else LIST_DISPATCH(float, const float*);
-#undef LIST_DISPATCH
-#undef LIST_LAUNCH
-#undef LIST_LAUNCH_D
+  const int iters = pipe_iters(d);
+  with_xt_saga(x_is_bf16, 0, [&](auto xt, auto) {
+    using XT = decltype(xt);
+    with_pipe_shape(iters, pipe_depth(iters, false), [&](auto IT, auto DP) {
+      constexpr int it = decltype(IT)::value, dp = decltype(DP)::value;
+      hipLaunchKernelGGL((grad_dense_list_kernel<XT, 256, dp, it>),
+                         dim3(grid), dim3(256), list_lds_bytes(it), stream,
+                         (const XT*)X, w, g_part, rowlist, ylist, count_dev,
+                         n_rows, d, objective);
+    });
+  });
+}
+
+// the flag-less entry points are null-flag wrappers
+void launch_grad_dense_flag(
+    const void* X, const float* y, const float* w, float* g_out,
+    float* g_part, int* n_out, const int* k_dev, long n_rows, int d,
+    uint64_t seed, uint32_t round_k, uint64_t row_start, double rate,
+    int objective, int x_is_bf16, hipStream_t stream,
+    unsigned long long* done_flag, unsigned long long done_val,
+    unsigned long long* done_arr) {
+  launch_dense(X, y, w, g_out, g_part, n_out, nullptr, nullptr, nullptr,
+               nullptr, k_dev, 0, n_rows, d, seed, round_k, row_start, rate,
+               objective, x_is_bf16, 0, stream, done_flag, done_val,
+               done_arr);
+}
+
+void launch_saga_grad_dense_flag(
+    const void* X, const float* y, const float* w, float* alpha,
+    float* g_out, float* g_part, int* n_out, int* idx_out, float* e_out,
+    int* pos_ctr, const int* k_dev, int commit_now, long n_rows, int d,
+    uint64_t seed, uint32_t round_k, uint64_t row_start, double rate,
+    int objective, int x_is_bf16, hipStream_t stream,
+    unsigned long long* done_flag, unsigned long long done_val,
+    unsigned long long* done_arr) {
+  launch_dense(X, y, w, g_out, g_part, n_out, alpha, idx_out, e_out, pos_ctr,
+               k_dev, commit_now, n_rows, d, seed, round_k, row_start, rate,
+               objective, x_is_bf16, 1, stream, done_flag, done_val,
+               done_arr);
 }
 
 void launch_grad_dense(const void* X, const float* y, const float* w,
@@ -1712,16 +1600,9 @@ void launch_grad_dense(const void* X, const float* y, const float* w,
                        const int* k_dev, long n_rows, int d, uint64_t seed,
                        uint32_t round_k, uint64_t row_start, double rate,
                        int objective, int x_is_bf16, hipStream_t stream) {
-  if (x_is_bf16)
-    launch_dense<__hip_bfloat16, false>(
-        (const __hip_bfloat16*)X, y, w, g_out, g_part, n_out, nullptr,
-        nullptr, nullptr, nullptr, k_dev, 0, n_rows, d, seed, round_k,
-        row_start, rate, objective, stream);
-  else
-    launch_dense<float, false>((const float*)X, y, w, g_out, g_part, n_out,
-                               nullptr, nullptr, nullptr, nullptr, k_dev, 0,
-                               n_rows, d, seed, round_k, row_start, rate,
-                               objective, stream);
+  launch_grad_dense_flag(X, y, w, g_out, g_part, n_out, k_dev, n_rows, d,
+                         seed, round_k, row_start, rate, objective,
+                         x_is_bf16, stream, nullptr, 0, nullptr);
 }
 
 void launch_saga_grad_dense(const void* X, const float* y, const float* w,
@@ -1732,36 +1613,10 @@ void launch_saga_grad_dense(const void* X, const float* y, const float* w,
                             uint32_t round_k, uint64_t row_start, double rate,
                             int objective, int x_is_bf16,
                             hipStream_t stream) {
-  if (x_is_bf16)
-    launch_dense<__hip_bfloat16, true>(
-        (const __hip_bfloat16*)X, y, w, g_out, g_part, n_out, alpha, idx_out,
-        e_out, pos_ctr, k_dev, commit_now, n_rows, d, seed, round_k,
-        row_start, rate, objective, stream);
-  else
-    launch_dense<float, true>((const float*)X, y, w, g_out, g_part, n_out,
-                              alpha, idx_out, e_out, pos_ctr, k_dev,
-                              commit_now, n_rows, d, seed, round_k, row_start,
-                              rate, objective, stream);
-}
-
-void launch_grad_dense_flag(
-    const void* X, const float* y, const float* w, float* g_out,
-    float* g_part, int* n_out, const int* k_dev, long n_rows, int d,
-    uint64_t seed, uint32_t round_k, uint64_t row_start, double rate,
-    int objective, int x_is_bf16, hipStream_t stream,
-    unsigned long long* done_flag, unsigned long long done_val,
-    unsigned long long* done_arr) {
-  if (x_is_bf16)
-    launch_dense<__hip_bfloat16, false>(
-        (const __hip_bfloat16*)X, y, w, g_out, g_part, n_out, nullptr,
-        nullptr, nullptr, nullptr, k_dev, 0, n_rows, d, seed, round_k,
-        row_start, rate, objective, stream, done_flag, done_val, done_arr);
-  else
-    launch_dense<float, false>((const float*)X, y, w, g_out, g_part, n_out,
-                               nullptr, nullptr, nullptr, nullptr, k_dev, 0,
-                               n_rows, d, seed, round_k, row_start, rate,
-                               objective, stream, done_flag, done_val,
-                               done_arr);
+  launch_saga_grad_dense_flag(X, y, w, alpha, g_out, g_part, n_out, idx_out,
+                              e_out, pos_ctr, k_dev, commit_now, n_rows, d,
+                              seed, round_k, row_start, rate, objective,
+                              x_is_bf16, stream, nullptr, 0, nullptr);
 }
 
 void launch_grad_dense_wave(const void* slots_dev, const void* cmd_host,
@@ -1774,7 +1629,7 @@ void launch_grad_dense_wave(const void* slots_dev, const void* cmd_host,
   const int grid = cmd->n * cmd->bper;
   const int iters = pipe_iters(d);
   (void)max_rows;
-  auto go = [&](auto xt, auto sg) {
+  with_xt_saga(x_is_bf16, saga, [&](auto xt, auto sg) {
     using XT = decltype(xt);
     constexpr bool SG = decltype(sg)::value;
     with_pipe_shape(iters, pipe_depth(iters, true), [&](auto IT, auto DP) {
@@ -1785,14 +1640,7 @@ void launch_grad_dense_wave(const void* slots_dev, const void* cmd_host,
                          (const GradWaveSlot*)slots_dev, *cmd, d, seed, thr,
                          take_all, objective);
     });
-  };
-  if (x_is_bf16) {
-    if (saga) go(__hip_bfloat16{}, std::true_type{});
-    else go(__hip_bfloat16{}, std::false_type{});
-  } else {
-    if (saga) go(float{}, std::true_type{});
-    else go(float{}, std::false_type{});
-  }
+  });
 }
 
 // What a dense gradient launch at feature dim d will run: fills
@@ -1805,7 +1653,7 @@ int query_dense_kernel(int d, int x_is_bf16, int saga, int wave, int* out) {
   if (d <= 0 || d % 4 != 0 || d > 2048) return -1;
   const int iters = pipe_iters(d);
   int rc = 0;
-  auto go = [&](auto xt, auto sg) {
+  with_xt_saga(x_is_bf16, saga, [&](auto xt, auto sg) {
     using XT = decltype(xt);
     constexpr bool SG = decltype(sg)::value;
     with_pipe_shape(iters, pipe_depth(iters, wave != 0),
@@ -1826,14 +1674,7 @@ int query_dense_kernel(int d, int x_is_bf16, int saga, int wave, int* out) {
       out[3] = attr.numRegs; out[4] = (int)attr.localSizeBytes;
       out[5] = (int)Shape::LDS; out[6] = nb; out[7] = 0;
     });
-  };
-  if (x_is_bf16) {
-    if (saga) go(__hip_bfloat16{}, std::true_type{});
-    else go(__hip_bfloat16{}, std::false_type{});
-  } else {
-    if (saga) go(float{}, std::true_type{});
-    else go(float{}, std::false_type{});
-  }
+  });
   return rc;
 }
 
@@ -1856,35 +1697,19 @@ void launch_alpha_gather_wave(const void* slots_dev, const void* cmd_host,
                      (const GradWaveSlot*)slots_dev, *cmd);
 }
 
-void launch_saga_grad_dense_flag(
-    const void* X, const float* y, const float* w, float* alpha,
-    float* g_out, float* g_part, int* n_out, int* idx_out, float* e_out,
-    int* pos_ctr, const int* k_dev, int commit_now, long n_rows, int d,
-    uint64_t seed, uint32_t round_k, uint64_t row_start, double rate,
-    int objective, int x_is_bf16, hipStream_t stream,
-    unsigned long long* done_flag, unsigned long long done_val,
-    unsigned long long* done_arr) {
-  if (x_is_bf16)
-    launch_dense<__hip_bfloat16, true>(
-        (const __hip_bfloat16*)X, y, w, g_out, g_part, n_out, alpha, idx_out,
-        e_out, pos_ctr, k_dev, commit_now, n_rows, d, seed, round_k,
-        row_start, rate, objective, stream, done_flag, done_val, done_arr);
-  else
-    launch_dense<float, true>((const float*)X, y, w, g_out, g_part, n_out,
-                              alpha, idx_out, e_out, pos_ctr, k_dev,
-                              commit_now, n_rows, d, seed, round_k, row_start,
-                              rate, objective, stream, done_flag, done_val,
-                              done_arr);
-}
-
-// event-free CSR launchers keep their original names as null-flag wrappers
 void launch_grad_csr_flag(
     const int* indptr, const int* indices, const void* values,
     const float* y, const float* w, float* g_out, int* n_out,
     const int* k_dev, long n_rows, uint64_t seed, uint32_t round_k,
     uint64_t row_start, double rate, int objective, int v_is_bf16,
     hipStream_t stream, unsigned long long* done_flag,
-    unsigned long long done_val, unsigned long long* done_arr);
+    unsigned long long done_val, unsigned long long* done_arr) {
+  launch_csr(indptr, indices, values, y, w, nullptr, g_out, n_out, nullptr,
+             nullptr, nullptr, k_dev, 0, n_rows, seed, round_k, row_start,
+             rate, objective, v_is_bf16, 0, stream, done_flag, done_val,
+             done_arr);
+}
+
 void launch_saga_grad_csr_flag(
     const int* indptr, const int* indices, const void* values,
     const float* y, const float* w, float* alpha, float* g_out, int* n_out,
@@ -1892,7 +1717,12 @@ void launch_saga_grad_csr_flag(
     int commit_now, long n_rows, uint64_t seed, uint32_t round_k,
     uint64_t row_start, double rate, int objective, int v_is_bf16,
     hipStream_t stream, unsigned long long* done_flag,
-    unsigned long long done_val, unsigned long long* done_arr);
+    unsigned long long done_val, unsigned long long* done_arr) {
+  launch_csr(indptr, indices, values, y, w, alpha, g_out, n_out, idx_out,
+             e_out, pos_ctr, k_dev, commit_now, n_rows, seed, round_k,
+             row_start, rate, objective, v_is_bf16, 1, stream, done_flag,
+             done_val, done_arr);
+}
 
 void launch_grad_csr(const int* indptr, const int* indices,
                      const void* values, const float* y, const float* w,
@@ -1927,12 +1757,6 @@ void launch_reduce_partials(const float* g_part, float* g_out, int d, int G,
                      0, stream, g_part, g_out, d, G, splits);
 }
 
-static inline int csr_lpr() {
-  const char* s = std::getenv("ASYNCAMD_CSR_LPR");
-  const int v = s ? std::atoi(s) : 32;  // measured best on rcv1 shape
-  return (v == 8 || v == 16 || v == 32 || v == 64) ? v : 32;
-}
-
 void launch_grad_csr_wave(const void* slots_dev, const void* cmd_host,
                           uint64_t seed, double rate, int objective,
                           int v_is_bf16, int saga, hipStream_t stream) {
@@ -1940,29 +1764,16 @@ void launch_grad_csr_wave(const void* slots_dev, const void* cmd_host,
   const uint32_t thr = philox_threshold(rate);
   const int take_all = rate >= 1.0;
   const int grid = cmd->n * cmd->bper;
-  const int lpr = csr_lpr();
-#define CSRW_LAUNCH(VT, SG, L)                                               \
-  hipLaunchKernelGGL((grad_csr_wave_kernel<VT, SG, L>), dim3(grid),          \
-                     dim3(BLOCK), 0, stream,                                 \
-                     (const CsrWaveSlot*)slots_dev, *cmd, seed, thr,         \
-                     take_all, objective)
-#define CSRW_LPR(VT, SG)                                                     \
-  do {                                                                       \
-    if (lpr == 8) CSRW_LAUNCH(VT, SG, 8);                                    \
-    else if (lpr == 32) CSRW_LAUNCH(VT, SG, 32);                             \
-    else if (lpr == 64) CSRW_LAUNCH(VT, SG, 64);                             \
-    else CSRW_LAUNCH(VT, SG, 16);                                            \
-  } while (0)
-#define CSRW_DISPATCH(VT)                                                    \
-  do {                                                                       \
-    if (saga) CSRW_LPR(VT, true);                                            \
-    else CSRW_LPR(VT, false);                                                \
-  } while (0)
-  if (v_is_bf16) CSRW_DISPATCH(__hip_bfloat16);
-  else CSRW_DISPATCH(float);
-#undef CSRW_DISPATCH
-#undef CSRW_LPR
-#undef CSRW_LAUNCH
+  with_xt_saga(v_is_bf16, saga, [&](auto vt, auto sg) {
+    with_const<8, 32, 64, 16>(csr_lpr(), [&](auto L) {
+      hipLaunchKernelGGL((grad_csr_wave_kernel<decltype(vt),
+                                               decltype(sg)::value,
+                                               decltype(L)::value>),
+                         dim3(grid), dim3(BLOCK), 0, stream,
+                         (const CsrWaveSlot*)slots_dev, *cmd, seed, thr,
+                         take_all, objective);
+    });
+  });
 }
 
 void launch_saga_commit_wave(const void* slots_dev, const void* cmd_host,
@@ -1973,109 +1784,28 @@ void launch_saga_commit_wave(const void* slots_dev, const void* cmd_host,
                      stream, (const CommitSlot*)slots_dev, *cmd);
 }
 
-void launch_grad_csr_flag(
-    const int* indptr, const int* indices, const void* values,
-    const float* y, const float* w, float* g_out, int* n_out,
-    const int* k_dev, long n_rows, uint64_t seed, uint32_t round_k,
-    uint64_t row_start, double rate, int objective, int v_is_bf16,
-    hipStream_t stream, unsigned long long* done_flag,
-    unsigned long long done_val, unsigned long long* done_arr) {
-  const uint32_t thr = philox_threshold(rate);
-  const int take_all = rate >= 1.0;
-  const int grid = grad_grid(n_rows);
-  const int lpr = csr_lpr();
-#define CSR_LAUNCH(VT, CAST, L)                                              \
-  hipLaunchKernelGGL((grad_csr_kernel<VT, false, L>), dim3(grid),            \
-                     dim3(BLOCK), 0, stream, indptr, indices, (CAST)values,  \
-                     y, w, g_out, n_out, nullptr, nullptr, nullptr, nullptr, \
-                     k_dev, 0, n_rows, seed, round_k, row_start, thr,        \
-                     take_all, objective, done_flag, done_val, done_arr)
-#define CSR_DISPATCH(VT, CAST)                                               \
-  do {                                                                       \
-    if (lpr == 8) CSR_LAUNCH(VT, CAST, 8);                                   \
-    else if (lpr == 32) CSR_LAUNCH(VT, CAST, 32);                            \
-    else if (lpr == 64) CSR_LAUNCH(VT, CAST, 64);                            \
-    else CSR_LAUNCH(VT, CAST, 16);                                           \
-  } while (0)
-  if (v_is_bf16) CSR_DISPATCH(__hip_bfloat16, const __hip_bfloat16*);
-  else CSR_DISPATCH(float, const float*);
-#undef CSR_DISPATCH
-#undef CSR_LAUNCH
-}
-
-void launch_saga_grad_csr_flag(
-    const int* indptr, const int* indices, const void* values,
-    const float* y, const float* w, float* alpha, float* g_out, int* n_out,
-    int* idx_out, float* e_out, int* pos_ctr, const int* k_dev,
-    int commit_now, long n_rows, uint64_t seed, uint32_t round_k,
-    uint64_t row_start, double rate, int objective, int v_is_bf16,
-    hipStream_t stream, unsigned long long* done_flag,
-    unsigned long long done_val, unsigned long long* done_arr) {
-  const uint32_t thr = philox_threshold(rate);
-  const int take_all = rate >= 1.0;
-  const int grid = grad_grid(n_rows);
-  const int lpr = csr_lpr();
-#define CSR_SLAUNCH(VT, CAST, L)                                             \
-  hipLaunchKernelGGL((grad_csr_kernel<VT, true, L>), dim3(grid),             \
-                     dim3(BLOCK), 0, stream, indptr, indices, (CAST)values,  \
-                     y, w, g_out, n_out, alpha, idx_out, e_out, pos_ctr,     \
-                     k_dev, commit_now, n_rows, seed, round_k, row_start,    \
-                     thr, take_all, objective, done_flag, done_val,          \
-                     done_arr)
-#define CSR_SDISPATCH(VT, CAST)                                              \
-  do {                                                                       \
-    if (lpr == 8) CSR_SLAUNCH(VT, CAST, 8);                                  \
-    else if (lpr == 32) CSR_SLAUNCH(VT, CAST, 32);                           \
-    else if (lpr == 64) CSR_SLAUNCH(VT, CAST, 64);                           \
-    else CSR_SLAUNCH(VT, CAST, 16);                                          \
-  } while (0)
-  if (v_is_bf16) CSR_SDISPATCH(__hip_bfloat16, const __hip_bfloat16*);
-  else CSR_SDISPATCH(float, const float*);
-#undef CSR_SDISPATCH
-#undef CSR_SLAUNCH
-}
-
 // l2 == l1 == 0 dispatches to the REG=false instantiation (the unchanged
 // body): the unregularised bits never depend on x*1.0 or x-0.0.
 void launch_sgd_update(float* w, const float* g, float gamma_k,
                        float inv_batch, int d, float l2, float l1,
                        hipStream_t stream) {
   const int grid = (d + 255) / 256;
-  if (l2 != 0.f || l1 != 0.f)
-    hipLaunchKernelGGL(sgd_update_kernel<true>, dim3(grid), dim3(256), 0,
-                       stream, w, g, gamma_k, inv_batch, d, l2, l1);
-  else
-    hipLaunchKernelGGL(sgd_update_kernel<false>, dim3(grid), dim3(256), 0,
-                       stream, w, g, gamma_k, inv_batch, d, l2, l1);
+  with_bool(l2 != 0.f || l1 != 0.f, [&](auto R) {
+    hipLaunchKernelGGL(sgd_update_kernel<decltype(R)::value>, dim3(grid),
+                       dim3(256), 0, stream, w, g, gamma_k, inv_batch, d, l2,
+                       l1);
+  });
 }
 
 void launch_saga_update(float* w, const float* g, float* alpha_bar,
                         float gamma, float inv_batch, float inv_N, int d,
                         float l2, float l1, hipStream_t stream) {
   const int grid = (d + 255) / 256;
-  if (l2 != 0.f || l1 != 0.f)
-    hipLaunchKernelGGL(saga_update_kernel<true>, dim3(grid), dim3(256), 0,
-                       stream, w, g, alpha_bar, gamma, inv_batch, inv_N, d,
-                       l2, l1);
-  else
-    hipLaunchKernelGGL(saga_update_kernel<false>, dim3(grid), dim3(256), 0,
-                       stream, w, g, alpha_bar, gamma, inv_batch, inv_N, d,
-                       l2, l1);
-}
-
-void launch_sgd_update_zero(float* w, float* g, float gamma_k,
-                            float inv_batch, int d, hipStream_t stream) {
-  const int grid = (d + 255) / 256;
-  hipLaunchKernelGGL(sgd_update_zero_kernel, dim3(grid), dim3(256), 0,
-                     stream, w, g, gamma_k, inv_batch, d);
-}
-
-void launch_saga_update_zero(float* w, float* g, float* alpha_bar,
-                             float gamma, float inv_batch, float inv_N,
-                             int d, hipStream_t stream) {
-  const int grid = (d + 255) / 256;
-  hipLaunchKernelGGL(saga_update_zero_kernel, dim3(grid), dim3(256), 0,
-                     stream, w, g, alpha_bar, gamma, inv_batch, inv_N, d);
+  with_bool(l2 != 0.f || l1 != 0.f, [&](auto R) {
+    hipLaunchKernelGGL(saga_update_kernel<decltype(R)::value>, dim3(grid),
+                       dim3(256), 0, stream, w, g, alpha_bar, gamma,
+                       inv_batch, inv_N, d, l2, l1);
+  });
 }
 
 void launch_saga_commit(float* alpha, const int* idx, const float* e, int n,
@@ -2122,19 +1852,14 @@ void launch_multi_update(float* w, float* const* g_tab,
   int grid = (nel + MU_BLOCK - 1) / MU_BLOCK;
   if (grid > 4096) grid = 4096;
   if (grid < 1) grid = 1;
-  const bool reg = l2 != 0.f || l1 != 0.f;
-#define MU_LAUNCH(V, R)                                                      \
-  hipLaunchKernelGGL((multi_update_kernel<V, R>), dim3(grid),                \
-                     dim3(MU_BLOCK), 0, stream, w, g_tab, wbuf_tab,          \
-                     alpha_bar, gamma, inv_batch, inv_N, d, l2, l1, *a)
-  if (vec4) {
-    if (reg) MU_LAUNCH(true, true);
-    else MU_LAUNCH(true, false);
-  } else {
-    if (reg) MU_LAUNCH(false, true);
-    else MU_LAUNCH(false, false);
-  }
-#undef MU_LAUNCH
+  with_bool(vec4 != 0, [&](auto V) {
+    with_bool(l2 != 0.f || l1 != 0.f, [&](auto R) {
+      hipLaunchKernelGGL(
+          (multi_update_kernel<decltype(V)::value, decltype(R)::value>),
+          dim3(grid), dim3(MU_BLOCK), 0, stream, w, g_tab, wbuf_tab,
+          alpha_bar, gamma, inv_batch, inv_N, d, l2, l1, *a);
+    });
+  });
 }
 
 // One barrier round of the native engine's synchronous mode. The work is
@@ -2155,20 +1880,15 @@ void launch_sync_round_update(float* w, float* const* g_tab,
   int grid = (n + SRU_BLOCK - 1) / SRU_BLOCK;
   if (grid > 1024) grid = 1024;
   if (grid < 1) grid = 1;
-  const bool reg = l2 != 0.f || l1 != 0.f;
-#define SRU_LAUNCH(V, R)                                                     \
-  hipLaunchKernelGGL((sync_round_update_kernel<V, R>), dim3(grid),           \
-                     dim3(SRU_BLOCK), 0, stream, w, g_tab, ctr_tab,          \
-                     alpha_bar, snap_dst, ticket, P, d, mode, scale, gamma,  \
-                     inv_batch, inv_N, eta, l2, l1)
-  if (vec4) {
-    if (reg) SRU_LAUNCH(true, true);
-    else SRU_LAUNCH(true, false);
-  } else {
-    if (reg) SRU_LAUNCH(false, true);
-    else SRU_LAUNCH(false, false);
-  }
-#undef SRU_LAUNCH
+  with_bool(vec4 != 0, [&](auto V) {
+    with_bool(l2 != 0.f || l1 != 0.f, [&](auto R) {
+      hipLaunchKernelGGL(
+          (sync_round_update_kernel<decltype(V)::value, decltype(R)::value>),
+          dim3(grid), dim3(SRU_BLOCK), 0, stream, w, g_tab, ctr_tab,
+          alpha_bar, snap_dst, ticket, P, d, mode, scale, gamma, inv_batch,
+          inv_N, eta, l2, l1);
+    });
+  });
 }
 
 // Compiled resource use of one update-kernel instantiation: sync = 0

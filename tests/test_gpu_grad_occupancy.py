@@ -144,6 +144,105 @@ def test_single_block_queue_chunks_saga(rate, monkeypatch):
     assert rel < 2e-4, f"rel err {rel}"
 
 
+# ------------------------------------- list form (scan_rows + grad_dense_list)
+
+def _list_grad(X, y, w, seed, round_k, rate):
+    """The graph engine's split form, launched directly: scan_rows fills the
+    compacted row list, grad_dense_list writes per-block partials,
+    reduce_partials sums them. Returns (g, listed row count)."""
+    core = _core()
+    n, d = X.shape
+    st = torch.cuda.current_stream().cuda_stream
+    G = int(core.grad_grid(n))
+    rowlist = torch.zeros(n, dtype=torch.int32, device="cuda")
+    ylist = torch.zeros(n, device="cuda")
+    count = torch.zeros(1, dtype=torch.int32, device="cuda")
+    g_part = torch.zeros(d * G, device="cuda")
+    g = torch.zeros(d, device="cuda")
+    core.scan_rows(y.data_ptr(), rowlist.data_ptr(), ylist.data_ptr(),
+                   count.data_ptr(), 0, n, seed, round_k, 0, rate, st)
+    core.grad_dense_list(X.data_ptr(), w.data_ptr(), g_part.data_ptr(),
+                         rowlist.data_ptr(), ylist.data_ptr(),
+                         count.data_ptr(), n, d, 0,
+                         1 if X.dtype == torch.bfloat16 else 0, st)
+    core.reduce_partials(g_part.data_ptr(), g.data_ptr(), d, G, 1, st)
+    torch.cuda.synchronize()
+    return g, int(count.item())
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("d", [4, 260, 2048])
+def test_list_form_matches_ref(d, dtype):
+    """The row-bounds shapes through the list kernel: one active lane, one
+    lane in the tail iteration, full ITERS=8. The listed-row count is no
+    multiple of DEPTH * waves, so the pipeline ends on clamped tail slots."""
+    n = _RB_N
+    X, y, w = _dense(n, d, seed=100 + d, dtype=dtype)
+    m = bernoulli_mask(_RB_SEED, _RB_ROUND, 0, n, _RB_RATE)
+    assert int(m.sum()) % 16 != 0
+    g, cnt = _list_grad(X, y, w, _RB_SEED, _RB_ROUND, _RB_RATE)
+    g_ref, cnt_ref = torch_ref.grad_dense(
+        X.float(), y, w, torch.from_numpy(m).cuda(), "lsq")
+    assert cnt == cnt_ref == int(m.sum())
+    rel = _rel(g, g_ref)
+    print(f"d={d} {dtype} rel={rel:.3e}")
+    assert rel < _tol(dtype), f"rel err {rel}"
+
+
+def test_list_form_depth_override(monkeypatch):
+    """ASYNCAMD_PIPE_DEPTH reaches the list kernel like the other pipelined
+    kernels: depth 1 (one row in flight per wave, every refill clamped or
+    one row ahead) computes the same gradient."""
+    monkeypatch.setenv("ASYNCAMD_PIPE_DEPTH", "1")
+    n, d = _RB_N, 260
+    X, y, w = _dense(n, d, seed=100 + d)
+    m = bernoulli_mask(_RB_SEED, _RB_ROUND, 0, n, _RB_RATE)
+    g, cnt = _list_grad(X, y, w, _RB_SEED, _RB_ROUND, _RB_RATE)
+    g_ref, cnt_ref = torch_ref.grad_dense(
+        X, y, w, torch.from_numpy(m).cuda(), "lsq")
+    assert cnt == cnt_ref == int(m.sum())
+    rel = _rel(g, g_ref)
+    print(f"rel={rel:.3e}")
+    assert rel < 2e-4, f"rel err {rel}"
+
+
+def test_list_form_single_block_chunks(monkeypatch):
+    """One block (ASYNCAMD_GRAD_GRID=1) owns the whole 5,000-row list and
+    walks it in three queue-capacity chunks, the last one partial."""
+    monkeypatch.setenv("ASYNCAMD_GRAD_GRID", "1")
+    n, d = 5000, 64
+    X, y, w = _dense(n, d, seed=34)
+    g, cnt = _list_grad(X, y, w, 17, 3, 1.0)
+    m = bernoulli_mask(17, 3, 0, n, 1.0)
+    assert int(m.sum()) == n > 2 * 2048
+    g_ref, cnt_ref = torch_ref.grad_dense(
+        X, y, w, torch.from_numpy(m).cuda(), "lsq")
+    assert cnt == cnt_ref == n
+    rel = _rel(g, g_ref)
+    print(f"rel={rel:.3e}")
+    assert rel < 2e-4, f"rel err {rel}"
+
+
+def test_list_form_ignores_neighbour_rows():
+    """test_row_bounds_ignore_neighbour_rows through the list kernel: every
+    unlisted row is NaN and none of it may reach g."""
+    n, d = _RB_N, 260
+    X, y, w = _dense(n, d, seed=100 + d)
+    m = bernoulli_mask(_RB_SEED, _RB_ROUND, 0, n, _RB_RATE)
+    assert m[-1] and not m.all()
+    mask = torch.from_numpy(m).cuda()
+    X_ref = X.clone()
+    X_ref[~mask] = 0
+    X[~mask] = float("nan")
+    g, cnt = _list_grad(X, y, w, _RB_SEED, _RB_ROUND, _RB_RATE)
+    g_ref, cnt_ref = torch_ref.grad_dense(X_ref, y, w, mask, "lsq")
+    assert cnt == cnt_ref == int(m.sum())
+    assert bool(torch.isfinite(g).all()), "neighbour-row NaN leaked into g"
+    rel = _rel(g, g_ref)
+    print(f"rel={rel:.3e}")
+    assert rel < 2e-4, f"rel err {rel}"
+
+
 # -------------------------------------------------------------- multi_update
 
 _MU_P = 32           # worker buffers in the tables
