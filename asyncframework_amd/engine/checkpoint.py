@@ -11,7 +11,7 @@ from __future__ import annotations
 
 import os
 import tempfile
-from typing import Dict, List, Optional
+from typing import Dict, Iterable, List, Optional
 
 import torch
 
@@ -72,48 +72,63 @@ def load_checkpoint(path: str) -> Dict:
     return torch.load(path, map_location="cpu", weights_only=True)
 
 
-def restore(server: Server, workers: Optional[List[Worker]], state: Dict
-            ) -> None:
-    """Load a snapshot back into a server + workers (devices preserved).
+def check_compatible(state: Dict, cfg,
+                     alpha_ids: Optional[Iterable[int]] = None,
+                     stacklevel: int = 2) -> List[int]:
+    """The one compatibility check every resume path runs before it copies
+    anything (restore(), the native dist server, the native local engine).
+
     The worker-pool shape must match: SAGA history tables are keyed by
     worker id over a fixed sharding, so resuming under a different
-    ``num_workers`` would silently mis-assign history."""
-    ck_P = state.get("cfg", {}).get("num_workers")
-    if ck_P is not None and ck_P != server.cfg.num_workers:
+    ``num_workers`` would silently mis-assign history — ValueError, as is a
+    ``d`` mismatch. A different l2/l1 only warns (the run continues on a
+    different objective). ``alpha_ids``: the worker ids whose history table
+    the caller is about to restore; those the checkpoint lacks are warned
+    about and returned (the caller leaves their tables as they are)."""
+    import warnings
+    ck_cfg = state.get("cfg", {})
+    ck_P = ck_cfg.get("num_workers")
+    if ck_P is not None and ck_P != cfg.num_workers:
         raise ValueError(
             f"checkpoint was taken with num_workers={ck_P}, cannot resume "
-            f"with num_workers={server.cfg.num_workers}")
-    if state.get("cfg", {}).get("d") not in (None, server.cfg.d):
+            f"with num_workers={cfg.num_workers}")
+    if ck_cfg.get("d") not in (None, cfg.d):
         raise ValueError("checkpoint dimensionality mismatch")
     # a checkpoint from before the penalties existed has neither key: 0.0
     for name in ("l2", "l1"):
-        ck_v = float(state.get("cfg", {}).get(name, 0.0))
-        now_v = float(getattr(server.cfg, name, 0.0))
+        ck_v = float(ck_cfg.get(name, 0.0))
+        now_v = float(getattr(cfg, name, 0.0))
         if ck_v != now_v:
-            import warnings
             warnings.warn(
                 f"checkpoint was taken with {name}={ck_v}, resuming with "
                 f"{name}={now_v}: the run continues on a different objective",
-                RuntimeWarning, stacklevel=2)
+                RuntimeWarning, stacklevel=stacklevel)
+    missing = [wid for wid in (alpha_ids or [])
+               if wid not in state.get("alpha", {})]
+    if missing:
+        # a checkpoint taken while a remote peer's snap sideband timed out
+        # has no table for that worker; resuming silently with zeroed SAGA
+        # history would corrupt the run's semantics — be loud about it.
+        warnings.warn(
+            f"checkpoint has no SAGA history table for worker(s) {missing}; "
+            "their alpha stays as-is (zeros on a fresh engine)",
+            RuntimeWarning, stacklevel=stacklevel)
+    return missing
+
+
+def restore(server: Server, workers: Optional[List[Worker]], state: Dict
+            ) -> None:
+    """Load a snapshot back into a server + workers (devices preserved),
+    after check_compatible."""
+    with_alpha = [wk for wk in workers or [] if wk.alpha is not None]
+    missing = check_compatible(state, server.cfg,
+                               alpha_ids=[wk.id for wk in with_alpha],
+                               stacklevel=3)
     server.k = int(state["k"])
     server.AC.setCurrentTime(int(state["current_time"]))
     server.w.copy_(state["w"].to(server.w.device))
     if state.get("alpha_bar") is not None and server.alpha_bar is not None:
         server.alpha_bar.copy_(state["alpha_bar"].to(server.alpha_bar.device))
-    missing = []
-    for wk in workers or []:
-        if wk.alpha is None:
-            continue
-        if wk.id in state["alpha"]:
+    for wk in with_alpha:
+        if wk.id not in missing:
             wk.alpha.copy_(state["alpha"][wk.id].to(wk.alpha.device))
-        else:
-            missing.append(wk.id)
-    if missing:
-        # a checkpoint taken while a remote peer's snap sideband timed out
-        # has no table for that worker; resuming silently with zeroed SAGA
-        # history would corrupt the run's semantics — be loud about it.
-        import warnings
-        warnings.warn(
-            f"checkpoint has no SAGA history table for worker(s) {missing}; "
-            "their alpha stays as-is (zeros on a fresh engine)",
-            RuntimeWarning, stacklevel=2)

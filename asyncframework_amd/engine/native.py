@@ -16,7 +16,13 @@ CPU tests and as the semantics oracle).
 per iteration — gradient wave over all P workers reading ``w`` itself, one
 fused round-update kernel, one host wait — with the same straggler model
 as SyncEngine + DelayInjector. Workers own no weight-snapshot buffer
-there, and the SAGA history must be device-resident."""
+there, and the SAGA history must be device-resident.
+
+Checkpoint / resume (both modes): the C++ loop ends every run — and, with
+``cfg.checkpoint_every``, reaches every checkpoint — in a quiescent state
+in which ``w``, ``alpha_bar`` and ``alpha_tables`` describe exactly iterate
+k; ``capture_state`` / ``restore_state`` move that state through the
+``engine/checkpoint.py`` schema shared with the other engines."""
 
 from __future__ import annotations
 
@@ -108,6 +114,58 @@ class NativeLocalEngine:
                 keep += [alpha, idx_out, e_out]
             self._keep.extend(keep)
             self._bufs.append(wd)
+        # start state of the next run(): None = fresh (k = clock = 0);
+        # restore_state() arms it, run() consumes it
+        self._start: Optional[Dict] = None
+
+    # -- checkpoint / resume (engine/checkpoint.py schema) -------------------
+
+    def capture_state(self, k: int, clock: int,
+                      delay_state: Optional[Dict] = None) -> Dict:
+        """The engine's tensors as a ``checkpoint.capture_state`` dict (CPU
+        clones; in spill mode the pinned master IS the table). Only valid
+        at a quiescent point: between run() calls, or inside the C++ loop's
+        checkpoint callback, which supplies ``k``, ``clock`` and the
+        straggler-calibration state (stored under ``native_delay``; the
+        other engines ignore the key)."""
+        state = {
+            "k": int(k),
+            "current_time": int(clock),
+            "w": self.w.detach().cpu().clone(),
+            "alpha_bar": (self.alpha_bar.detach().cpu().clone()
+                          if self.cfg.algo == "asaga" else None),
+            "cfg": self.cfg.__dict__.copy(),
+            "alpha": {wid: t.detach().cpu().clone()
+                      for wid, t in enumerate(self.alpha_tables)},
+        }
+        if delay_state is not None:
+            state["native_delay"] = {
+                "avg_delay_ms": float(delay_state["avg_delay_ms"]),
+                "delay_flag": bool(delay_state["delay_flag"]),
+                "cul_time_ms": float(delay_state["cul_time_ms"]),
+                "cul_count": int(delay_state["cul_count"])}
+        return state
+
+    def restore_state(self, state: Dict) -> None:
+        """Copy a checkpoint into the engine's tensors and arm the next
+        run() to continue from its k, arrival clock and (when the file
+        carries one) straggler-calibration state."""
+        from .checkpoint import check_compatible
+        missing = check_compatible(
+            state, self.cfg, alpha_ids=range(len(self.alpha_tables)),
+            stacklevel=3)
+        self.w.copy_(state["w"].to(self.device, dtype=torch.float32))
+        if self.cfg.algo == "asaga" and state.get("alpha_bar") is not None:
+            self.alpha_bar.copy_(
+                state["alpha_bar"].to(self.device, dtype=torch.float32))
+        for wid, table in enumerate(self.alpha_tables):
+            if wid not in missing:
+                table.copy_(state["alpha"][wid].to(table.device,
+                                                   dtype=torch.float32))
+        self._start = dict(k0=int(state["k"]),
+                           clock0=int(state["current_time"]))
+        if state.get("native_delay") is not None:
+            self._start["delay_state"] = dict(state["native_delay"])
 
     def run(self, num_iterations: Optional[int] = None,
             mark_lo: int = -1, mark_hi: int = -1,
@@ -117,9 +175,19 @@ class NativeLocalEngine:
         applied updates (the reference's printer_freq loss-curve mechanism)
         into a device ring, returned as res['opt_vars']. In sync mode
         iterations, marks and the snapshot cadence count ROUNDS (one update
-        per round), as SyncEngine does."""
+        per round), as SyncEngine does.
+
+        After restore_state() the run continues from the restored k
+        (``num_iterations`` stays the TOTAL target; times restart at 0 and
+        opt_vars[0] is the restored w). With ``cfg.checkpoint_every > 0 and
+        cfg.checkpoint_path`` the loop quiesces whenever k crosses a
+        multiple of checkpoint_every and the state is written with
+        ``checkpoint.save_state``."""
         cfg = self.cfg
         iters = num_iterations or cfg.num_iterations
+        start, self._start = self._start, None
+        w_start = (self.w.detach().cpu().clone() if start is not None
+                   else torch.zeros(cfg.d))
         snap_ring = None
         snap_cap = 0
         if snapshot_every > 0:
@@ -139,20 +207,35 @@ class NativeLocalEngine:
                     snap_ring=snap_ring.data_ptr() if snap_ring is not None
                     else 0, snap_cap=snap_cap, l2=float(cfg.l2),
                     l1=float(cfg.l1))
+        if start is not None:
+            conf.update(start)
+        ckpt_cb = None
+        if cfg.checkpoint_every > 0 and cfg.checkpoint_path:
+            from .checkpoint import save_state
+            conf["ckpt_every"] = int(cfg.checkpoint_every)
+
+            def ckpt_cb(info):
+                # called by the C++ loop at a quiescent point, GIL held,
+                # every engine stream idle
+                save_state(cfg.checkpoint_path,
+                           self.capture_state(info["k"], info["clock"],
+                                              info["delay_state"]))
         torch.cuda.synchronize()
         if cfg.sync:
             res = self._core.native_sync_run(conf, self._bufs,
                                              self.w.data_ptr(),
                                              self.alpha_bar.data_ptr(),
-                                             _SYNC_MODE[cfg.algo])
+                                             _SYNC_MODE[cfg.algo], ckpt_cb)
         else:
             res = self._core.native_local_run(conf, self._bufs,
                                               self.w.data_ptr(),
-                                              self.alpha_bar.data_ptr())
+                                              self.alpha_bar.data_ptr(),
+                                              ckpt_cb)
         torch.cuda.synchronize()
+        res["k0"] = start["k0"] if start is not None else 0
         if snapshot_every > 0:
             snaps = res["snap_ms"]
-            res["opt_vars"] = [(0, torch.zeros(cfg.d))] + [
+            res["opt_vars"] = [(0, w_start)] + [
                 (int(ms), snap_ring[i].cpu().clone())
                 for i, ms in enumerate(snaps)]
         return res

@@ -83,12 +83,10 @@ def run_engine(cfg: EngineConfig, workers: List[Worker],
     """engine='threads' (the Python mailbox engine — CPU + semantics
     oracle) or 'native' (the C++ engine, GPU only: the async event loop, or
     for ``cfg.sync`` its stream-ordered synchronous rounds).
-    ``resume_from`` restores a checkpoint (threads engine only)."""
+    ``resume_from`` restores a checkpoint first; both engines read and
+    write the one engine/checkpoint.py schema (``cfg.checkpoint_path`` +
+    ``cfg.checkpoint_every``), so a file from either resumes on the other."""
     if engine == "native":
-        assert not resume_from, "resume is a threads-engine feature"
-        assert not (cfg.checkpoint_every > 0 and cfg.checkpoint_path), \
-            ("checkpointing with the single-GPU native engine is not wired "
-             "— use --engine threads (the dist engines support it)")
         if cfg.sync:
             # first, before the extension is imported or anything allocated
             assert workers[0].device.type == "cuda", \
@@ -96,13 +94,19 @@ def run_engine(cfg: EngineConfig, workers: List[Worker],
         from .engine.native import NativeLocalEngine
         neng = NativeLocalEngine(cfg, [w.shard for w in workers],
                                  workers[0].device)
+        if resume_from:
+            from .engine.checkpoint import load_checkpoint
+            neng.restore_state(load_checkpoint(resume_from))
         nres = neng.run(max_wall_s=max_wall_s or 1800.0,
                         snapshot_every=(cfg.printer_freq
                                         if cfg.snapshot_weights else 0))
         if verbose:
             # sync: k counts rounds — one line every printer_freq rounds,
-            # as SyncEngine prints them
-            for i in range(0, nres["k"], cfg.printer_freq):
+            # as SyncEngine prints them; a resumed run prints only the
+            # iterations of this process
+            pf = cfg.printer_freq
+            first = -(-nres["k0"] // pf) * pf
+            for i in range(first, nres["k"], pf):
                 print(f"Iteration {i} is finished")
         if cfg.sync:  # SyncEngine leaves waiting_time empty
             waiting = {}

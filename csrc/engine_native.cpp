@@ -57,6 +57,20 @@
 // wait, so loss-curve times are completion times, not enqueue times. The
 // wall cap is checked between rounds (as the Python SyncEngine does); a
 // round in flight is bounded by stall_s and throws with its k.
+//
+// Checkpoint / resume (both modes). Every run ENDS quiescent: after the
+// last time stamp, accepted-but-uncommitted SAGA history is committed and
+// the gradient buffers of dropped or rejected rounds are zeroed, so w,
+// alpha_bar and the history tables describe exactly iterate k. A run may
+// START at conf k0/clock0 (+ delay_state) instead of zero — step sizes,
+// Philox round keys, the snapshot cadence, the calibration window and the
+// marks all key on the absolute k, and iters stays the total target. With
+// conf ckpt_every > 0 the loop reaches the same quiescent state whenever k
+// crosses a multiple (async: stop dispatching, book the rounds in flight,
+// flush; sync: commit the round's staged history) and calls a Python
+// callable with {k, clock, delay_state} under the GIL; Python owns the
+// tensors and writes the file (engine/native.py, engine/checkpoint.py).
+// Off, the feature costs one integer compare per applied update.
 
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
@@ -71,6 +85,7 @@
 #include <cmath>
 #include <cstdint>
 #include <deque>
+#include <limits>
 #include <stdexcept>
 #include <string>
 #include <thread>
@@ -216,6 +231,10 @@ struct EngineCfg {
   uintptr_t snap_ring = 0;   // [snap_cap][d] device ring
   long snap_cap = 0;
   double l2 = 0.0, l1 = 0.0;  // elastic-net penalties (0/0: legacy kernels)
+  // resume / checkpoint (all optional; absent keys leave a fresh run)
+  long k0 = 0;          // initial k (iters stays the TOTAL target)
+  int clock0 = 0;       // initial arrival clock
+  long ckpt_every = 0;  // checkpoint when k crosses a multiple (0 = off)
 };
 
 double now_s() {
@@ -271,6 +290,23 @@ struct NativeEngine {
   // kernel's counter-reset ticket
   int** ctr_tab_dev = nullptr;
   int* sync_ticket_dev = nullptr;
+  bool sync_staged = false;  // the last sync SAGA round's history is staged
+  // periodic checkpoint: append_accepted / the sync loop compare k against
+  // next_ckpt (LONG_MAX when off — the only cost of the feature being off)
+  py::object ckpt_cb;  // Python callable({k, clock, delay_state}); GIL-guarded
+  long next_ckpt = std::numeric_limits<long>::max();
+  bool ckpt_due = false;
+  double ckpt_t_begin = 0;
+  long checkpoints = 0;
+  double checkpoint_ms = 0;  // host time quiesced, callback included
+
+  // Start state (fresh run: all zeros, as before).
+  void arm_start() {
+    k = cfg.k0;
+    clock = cfg.clock0;
+    if (cfg.ckpt_every > 0)
+      next_ckpt = (k / cfg.ckpt_every + 1) * cfg.ckpt_every;
+  }
 
   void init_stragglers() {
     straggler_kind.assign(cfg.P, 0);
@@ -632,6 +668,10 @@ struct NativeEngine {
     if (cfg.algo == 1) wk.pending_commit = true;
     k += 1;
     applied += 1;
+    if (k == next_ckpt) {  // never true with checkpointing off
+      ckpt_due = true;     // the loop quiesces after this sweep
+      ckpt_t_begin = t_now;
+    }
     if (snap_now || k == cfg.mark_lo || k == cfg.mark_hi || mu.n == MU_MAX)
       flush_batch(nullptr);
     if (snap_now) {
@@ -659,7 +699,101 @@ struct NativeEngine {
     double elapsed_ms = 0, mark_lo_t = 0, mark_hi_t = 0, avg_delay = 0;
     std::vector<double> waits;
     std::vector<double> snap_ms;
+    // resumable state + checkpoint accounting
+    int clock = 0;
+    bool delay_flag = false;
+    double cul_time_ms = 0;
+    long cul_count = 0;
+    long checkpoints = 0;
+    double checkpoint_ms = 0;
   };
+
+  void fill_result_state(Result& out) const {
+    out.clock = clock;
+    out.delay_flag = delay_flag;
+    out.cul_time_ms = cul_time_ms;
+    out.cul_count = cul_count;
+    out.checkpoints = checkpoints;
+    out.checkpoint_ms = checkpoint_ms;
+  }
+
+  // -- quiescent state + checkpoint callback -------------------------------
+
+  // Async mode. Precondition: no round is in flight and every worker / wave
+  // stream is drained. Commits every accepted-but-uncommitted SAGA round
+  // (pending_commit implies the worker has not been redispatched since, so
+  // its staging still holds that round) and zeroes every gradient buffer
+  // holding a rejected or dropped round, on the server stream, then waits.
+  // Afterwards w, alpha_bar and the history tables describe iterate k.
+  void flush_quiescent() {
+    if (cfg.algo == 1) {
+      if (commit_slots_dev) {
+        CsrCommitCmd cc;
+        cc.n = 0;
+        cc.bper = 16;
+        for (int i = 0; i < cfg.P; ++i) {
+          if (!ws[i].pending_commit) continue;
+          cc.wid[cc.n] = i;
+          cc.do_commit[cc.n] = 1;
+          cc.n += 1;
+          ws[i].pending_commit = false;
+        }
+        if (cc.n > 0) {
+          launch_saga_commit_wave(commit_slots_dev, &cc, sstream);
+          HIP_CHECK(hipGetLastError());
+        }
+      } else {
+        for (auto& wk : ws) {
+          if (!wk.pending_commit) continue;
+          float* dst = (float*)(wk.alpha_host ? wk.alpha_host : wk.alpha);
+          launch_saga_commit_devn(dst, (const int*)wk.idx_out,
+                                  (const float*)wk.e_out,
+                                  (const int*)(wk.ctr + 4), wk.saga_cap,
+                                  sstream);
+          HIP_CHECK(hipGetLastError());
+          wk.pending_commit = false;
+        }
+      }
+    }
+    for (auto& wk : ws) {
+      if (!wk.g_dirty) continue;
+      HIP_CHECK(hipMemsetAsync((void*)wk.g, 0, (size_t)cfg.d * 4, sstream));
+      wk.g_dirty = false;
+    }
+    HIP_CHECK(hipStreamSynchronize(sstream));
+  }
+
+  void drain_worker_streams() {
+    for (auto& wk : ws) HIP_CHECK(hipStreamSynchronize(wk.stream));
+    for (int i = 0; i < NWSTREAM; ++i)
+      if (wstreams[i]) HIP_CHECK(hipStreamSynchronize(wstreams[i]));
+  }
+
+  // Calls the Python checkpoint callback with the quiescent state's scalars
+  // (the tensors are Python's own). Every stream is idle here, so an
+  // exception from the callback can free the tables before it propagates.
+  void call_checkpoint() {
+    try {
+      py::gil_scoped_acquire gil;
+      py::dict ds;
+      ds["avg_delay_ms"] = avg_delay_ms;
+      ds["delay_flag"] = delay_flag;
+      ds["cul_time_ms"] = cul_time_ms;
+      ds["cul_count"] = cul_count;
+      py::dict st;
+      st["k"] = k;
+      st["clock"] = clock;
+      st["delay_state"] = ds;
+      ckpt_cb(st);
+    } catch (...) {
+      teardown_tables();
+      throw;
+    }
+    checkpoints += 1;
+    checkpoint_ms += (now_s() - ckpt_t_begin) * 1000.0;
+    ckpt_due = false;
+    next_ckpt = (k / cfg.ckpt_every + 1) * cfg.ckpt_every;
+  }
 
   // Streams, completion lines, wave slot tables and pointer tables shared
   // by run() and run_sync(). ``sync``: every worker reads the iterate w
@@ -880,13 +1014,88 @@ struct NativeEngine {
     }
   }
 
+  // One sweep over the workers' completion lines: book every finished
+  // round, append the accepted ones to the update batch. True when any
+  // round completed.
+  inline __attribute__((always_inline)) bool poll_sweep() {
+    bool any = false;
+    for (int i = 0; i < cfg.P && k < cfg.iters; ++i) {
+      WorkerBuf& wk = ws[i];
+      // NB round-1 regression: a `submit_t > finish_t` guard here was
+      // permanently false after dispatch() seeded finish_t = t_now on the
+      // first round (BENCH_r01 30-min 0%-GPU hang). !busy alone gates
+      // polling; busy is only set between dispatch and completion.
+      if (!wk.busy || !wk.in_flight) continue;
+      // event-free completion: the grad kernel's last block published
+      // round_serial to this pinned line (system-scope release store);
+      // a plain volatile read replaces hipEventQuery
+      if (*wk.done_flag == wk.round_serial) {
+        const double tc = now_s();
+        if (book_completion(i, tc)) append_accepted(i, tc);
+        any = true;
+      }
+    }
+    return any;
+  }
+
+  // Collect the dispatchable workers, apply the batch (writing their
+  // weight snapshots) and launch their rounds.
+  void redispatch(std::vector<int>& ready) {
+    ready.clear();
+    collect_ready(now_s(), ready);
+    // one kernel: apply the sweep's remaining accepted gradients AND
+    // write the post-batch w into the redispatching workers' snapshot
+    // buffers (replaces a 3 KB hipMemcpyAsync per dispatch)
+    flush_batch(&ready);
+    const double td = now_s();
+    if (wave_ok)
+      dispatch_wave(ready, td);
+    else
+      for (int wid : ready) dispatch_impl(wid, td, false);
+  }
+
+  // Periodic checkpoint (cold path, entered from the sweep in which k
+  // crossed a multiple of ckpt_every): dispatch nothing new, keep booking
+  // completions normally — tau filter, updates, k may advance — until no
+  // round is in flight; delayed stragglers stay delayed. Then the quiescent
+  // flush, the callback, and a redispatch of the idle workers against a
+  // fresh w. Returns early, leaving ckpt_due set, when the run ends first
+  // (k reached iters or the wall cap): run()'s quiescent end takes over.
+  void quiesce_and_checkpoint(double t0, double& last_progress,
+                              std::vector<int>& ready) {
+    flush_batch(nullptr);
+    while (true) {
+      bool flying = false;
+      for (auto& wk : ws) flying = flying || wk.in_flight;
+      if (!flying) break;
+      const double t_now = now_s();
+      if (k >= cfg.iters || t_now - t0 > cfg.max_wall_s) return;
+      if (t_now > last_progress + cfg.stall_s)
+        throw std::runtime_error(
+            "native engine stalled: no completion for " +
+            std::to_string(cfg.stall_s) + " s while quiescing for a "
+            "checkpoint at k=" + std::to_string(k));
+      if (poll_sweep()) {
+        last_progress = t_now;
+        flush_batch(nullptr);
+      }
+    }
+    drain_worker_streams();
+    flush_quiescent();
+    call_checkpoint();
+    last_progress = now_s();
+    if (k < cfg.iters) redispatch(ready);
+  }
+
   Result run() {
     setup_tables(false);
+    arm_start();
     for (int i = 0; i < cfg.P; ++i) pendingq.push_back(i);
     const double t0 = now_s();
     run_t0 = t0;
-    // first dispatch ignores the gate (reference k==0 path)
-    {
+    // first dispatch ignores the gate (reference k==0 path); a resume at
+    // k0 >= iters runs zero rounds
+    if (k < cfg.iters) {
       const size_t qn = pendingq.size();
       for (size_t i = 0; i < qn; ++i) {
         const int wid = pendingq.front();
@@ -930,36 +1139,12 @@ struct NativeEngine {
       // poll completions; accepted gradients accumulate into one batched
       // update kernel per sweep (append_accepted flushes early at snapshot
       // and bench-mark boundaries to keep per-update precision)
-      bool any = false;
-      for (int i = 0; i < cfg.P && k < cfg.iters; ++i) {
-        WorkerBuf& wk = ws[i];
-        // NB round-1 regression: a `submit_t > finish_t` guard here was
-        // permanently false after dispatch() seeded finish_t = t_now on the
-        // first round (BENCH_r01 30-min 0%-GPU hang). !busy alone gates
-        // polling; busy is only set between dispatch and completion.
-        if (!wk.busy || !wk.in_flight) continue;
-        // event-free completion: the grad kernel's last block published
-        // round_serial to this pinned line (system-scope release store);
-        // a plain volatile read replaces hipEventQuery
-        if (*wk.done_flag == wk.round_serial) {
-          const double tc = now_s();
-          if (book_completion(i, tc)) append_accepted(i, tc);
-          any = true;
-        }
-      }
-      if (any) {
+      if (poll_sweep()) {
         last_progress = t_now;
-        ready.clear();
-        collect_ready(now_s(), ready);
-        // one kernel: apply the sweep's remaining accepted gradients AND
-        // write the post-batch w into the redispatching workers' snapshot
-        // buffers (replaces a 3 KB hipMemcpyAsync per dispatch)
-        flush_batch(&ready);
-        const double td = now_s();
-        if (wave_ok)
-          dispatch_wave(ready, td);
+        if (ckpt_due)
+          quiesce_and_checkpoint(t0, last_progress, ready);
         else
-          for (int wid : ready) dispatch_impl(wid, td, false);
+          redispatch(ready);
       }
     }
     HIP_CHECK(hipStreamSynchronize(sstream));
@@ -968,9 +1153,18 @@ struct NativeEngine {
     // resumes — INCLUDING the wave streams: the final sweep may have
     // dispatched a wave whose kernels are still writing g/wbuf/alpha and
     // publishing to the pinned flags this teardown is about to free
-    for (auto& wk : ws) HIP_CHECK(hipStreamSynchronize(wk.stream));
-    for (int i = 0; i < NWSTREAM; ++i)
-      if (wstreams[i]) HIP_CHECK(hipStreamSynchronize(wstreams[i]));
+    drain_worker_streams();
+    // quiescent end (after the t1 stamp: reported times are unchanged).
+    // Rounds still in flight at exit are dropped — their sums are zeroed
+    // with the rejected rounds' — and every accepted round's history is
+    // committed, so w, alpha_bar and the tables describe exactly iterate k
+    for (auto& wk : ws)
+      if (wk.in_flight) {
+        wk.in_flight = false;
+        wk.g_dirty = true;
+      }
+    flush_quiescent();
+    if (ckpt_due) call_checkpoint();  // k crossed a multiple as the run ended
     Result out;
     out.k = k;
     out.elapsed_ms = (t1 - t0) * 1000.0;
@@ -982,33 +1176,27 @@ struct NativeEngine {
     out.avg_delay = avg_delay_ms;
     out.snap_ms = snap_ms;
     for (auto& wk : ws) out.waits.push_back(wk.waiting_ms);
+    fill_result_state(out);
     teardown_tables();
     return out;
   }
 
   // -- synchronous mode (see the file header) ------------------------------
 
-  // Round kr's gradient work, all on the server stream: (SAGA, kr > 0) the
-  // commit of round kr-1's staged history — every sync round is accepted —
-  // then one gradient wave over ALL P slots against w itself. Shapes the
+  // Round kr's gradient work, all on the server stream: (SAGA) the commit
+  // of the previous round's staged history, unless a checkpoint already
+  // committed it — every sync round is accepted — then one gradient wave
+  // over ALL P slots against w itself. Shapes the
   // wave kernels do not cover take the per-worker launch_grad on that same
   // stream (setup_tables(true) pointed wk.stream at sstream, wk.wbuf at w).
-  void sync_enqueue_grad(long kr) {
-    const long round_key = kr + 1;  // reference seed+k+1
-    if (!wave_ok) {
-      for (auto& wk : ws) {
-        if (cfg.algo == 1 && kr > 0) {
-          launch_saga_commit_devn((float*)wk.alpha, (const int*)wk.idx_out,
-                                  (const float*)wk.e_out,
-                                  (const int*)(wk.ctr + 4), wk.saga_cap,
-                                  sstream);
-          HIP_CHECK(hipGetLastError());
-        }
-        launch_grad(wk, round_key);  // SAGA: re-zeroes ctr after the commit
-      }
-      return;
-    }
-    if (cfg.algo == 1 && kr > 0) {
+  // Commit the previous sync SAGA round's staged history for all P workers
+  // on the server stream (no-op when nothing is staged). The wave kernel
+  // also resets the staging counters; the per-worker form leaves that to
+  // launch_grad's memset. Clearing sync_staged is what keeps the round
+  // after a checkpoint from committing the same staging again.
+  void sync_commit_staged() {
+    if (cfg.algo != 1 || !sync_staged) return;
+    if (commit_slots_dev) {
       CsrCommitCmd cc{};
       cc.n = cfg.P;
       cc.bper = 16;
@@ -1018,6 +1206,25 @@ struct NativeEngine {
       }
       launch_saga_commit_wave(commit_slots_dev, &cc, sstream);
       HIP_CHECK(hipGetLastError());
+    } else {
+      for (auto& wk : ws) {
+        launch_saga_commit_devn((float*)wk.alpha, (const int*)wk.idx_out,
+                                (const float*)wk.e_out,
+                                (const int*)(wk.ctr + 4), wk.saga_cap,
+                                sstream);
+        HIP_CHECK(hipGetLastError());
+      }
+    }
+    sync_staged = false;
+  }
+
+  void sync_enqueue_grad(long kr) {
+    const long round_key = kr + 1;  // reference seed+k+1
+    sync_commit_staged();
+    if (!wave_ok) {
+      // SAGA: launch_grad re-zeroes ctr after the commit
+      for (auto& wk : ws) launch_grad(wk, round_key);
+      return;
     }
     GradWaveCmd cmd{};
     cmd.n = cfg.P;
@@ -1059,9 +1266,19 @@ struct NativeEngine {
     (void)hipGetLastError();  // drop the polls' hipErrorNotReady
   }
 
+  // Commit whatever round kr staged and wait for it (bounded, like every
+  // wait of this path). Without staged history the stream is already idle.
+  void sync_quiesce(long kr) {
+    if (cfg.algo != 1 || !sync_staged) return;
+    sync_commit_staged();
+    HIP_CHECK(hipEventRecord(update_ev, sstream));
+    sync_wait_round(kr, now_s());
+  }
+
   // mode: 0 asgd, 1 asaga, 2 mllib (cfg.algo is 1 for asaga, else 0).
   Result run_sync(int mode) {
     setup_tables(true);
+    arm_start();
     bool vec4 = cfg.d % 4 == 0 &&
                 ((w | alpha_bar | cfg.snap_ring) & 15) == 0;
     for (auto& wk : ws) vec4 = vec4 && (wk.g & 15) == 0;
@@ -1131,11 +1348,20 @@ struct NativeEngine {
         cul_count += cfg.P;
       }
       if (snap_now) snap_ms.push_back((t1 - t0) * 1000.0);
+      sync_staged = mode == 1;
       k += 1;
       applied += 1;
       if (k == cfg.mark_lo) mark_lo_t = t1;
       if (k == cfg.mark_hi) mark_hi_t = t1;
+      if (k == next_ckpt) {  // never true with checkpointing off
+        ckpt_t_begin = now_s();
+        sync_quiesce(k - 1);
+        call_checkpoint();
+      }
     }
+    // quiescent end (after the last t1 stamp): the last round's staged
+    // history is committed, so the tables describe iterate k
+    sync_quiesce(k - 1);
     Result out;
     out.k = k;
     out.elapsed_ms = (t1 - t0) * 1000.0;
@@ -1147,6 +1373,7 @@ struct NativeEngine {
     out.avg_delay = avg_delay_ms;
     out.snap_ms = snap_ms;
     out.waits.assign(cfg.P, 0.0);
+    fill_result_state(out);
     teardown_tables();
     return out;
   }
@@ -1157,7 +1384,7 @@ struct NativeEngine {
 namespace {
 
 void fill_engine(NativeEngine& eng, py::dict c, py::list workers,
-                 uintptr_t w, uintptr_t alpha_bar) {
+                 uintptr_t w, uintptr_t alpha_bar, py::object ckpt_cb) {
   EngineCfg& cfg = eng.cfg;
   cfg.N = py::cast<long>(c["N"]);
   cfg.d = py::cast<int>(c["d"]);
@@ -1185,6 +1412,25 @@ void fill_engine(NativeEngine& eng, py::dict c, py::list workers,
   cfg.snap_every = py::cast<long>(c["snap_every"]);
   cfg.snap_ring = py::cast<uintptr_t>(c["snap_ring"]);
   cfg.snap_cap = py::cast<long>(c["snap_cap"]);
+  if (c.contains("k0")) cfg.k0 = py::cast<long>(c["k0"]);
+  if (c.contains("clock0")) cfg.clock0 = py::cast<int>(c["clock0"]);
+  if (c.contains("ckpt_every"))
+    cfg.ckpt_every = py::cast<long>(c["ckpt_every"]);
+  if (cfg.k0 < 0 || cfg.clock0 < 0 || cfg.ckpt_every < 0)
+    throw std::runtime_error(
+        "native engine: k0, clock0 and ckpt_every must be non-negative");
+  if (c.contains("delay_state")) {
+    // a resumed straggler run neither recalibrates nor runs undelayed
+    py::dict ds = py::cast<py::dict>(c["delay_state"]);
+    eng.avg_delay_ms = py::cast<double>(ds["avg_delay_ms"]);
+    eng.delay_flag = py::cast<bool>(ds["delay_flag"]);
+    eng.cul_time_ms = py::cast<double>(ds["cul_time_ms"]);
+    eng.cul_count = py::cast<long>(ds["cul_count"]);
+  }
+  if (cfg.ckpt_every > 0 && ckpt_cb.is_none())
+    throw std::runtime_error(
+        "native engine: ckpt_every > 0 needs a checkpoint callback");
+  if (cfg.ckpt_every > 0) eng.ckpt_cb = ckpt_cb;
   for (auto item : workers) {
     py::dict wd = py::cast<py::dict>(item);
     WorkerBuf wk;
@@ -1235,6 +1481,12 @@ py::dict result_dict(const NativeEngine::Result& r) {
   out["avg_delay_ms"] = r.avg_delay;
   out["waiting_ms"] = r.waits;
   out["snap_ms"] = r.snap_ms;
+  out["clock"] = r.clock;
+  out["delay_flag"] = r.delay_flag;
+  out["cul_time_ms"] = r.cul_time_ms;
+  out["cul_count"] = r.cul_count;
+  out["checkpoints"] = r.checkpoints;
+  out["checkpoint_ms"] = r.checkpoint_ms;
   return out;
 }
 
@@ -1243,27 +1495,32 @@ py::dict result_dict(const NativeEngine::Result& r) {
 void register_native_engine(py::module_& m) {
   m.def(
       "native_local_run",
-      [](py::dict c, py::list workers, uintptr_t w, uintptr_t alpha_bar) {
+      [](py::dict c, py::list workers, uintptr_t w, uintptr_t alpha_bar,
+         py::object ckpt_cb) {
         NativeEngine eng;
-        fill_engine(eng, c, workers, w, alpha_bar);
+        fill_engine(eng, c, workers, w, alpha_bar, ckpt_cb);
         NativeEngine::Result r;
         {
-          py::gil_scoped_release rel;  // the event loop never touches Python
+          // the event loop never touches Python, except to call ckpt_cb
+          // (GIL re-taken for that call alone) at a quiescent checkpoint
+          py::gil_scoped_release rel;
           r = eng.run();
         }
         return result_dict(r);
-      });
+      },
+      py::arg("conf"), py::arg("workers"), py::arg("w"),
+      py::arg("alpha_bar"), py::arg("ckpt_cb") = py::none());
   // Synchronous mode: same conf/worker dicts, plus mode 0 asgd / 1 asaga /
   // 2 mllib (conf["algo"] is 1 for asaga, else 0). Host-spill history is
   // not supported here (the Python adapter rejects it).
   m.def(
       "native_sync_run",
       [](py::dict c, py::list workers, uintptr_t w, uintptr_t alpha_bar,
-         int mode) {
+         int mode, py::object ckpt_cb) {
         if (mode < 0 || mode > 2)
           throw std::runtime_error("native sync engine: mode must be 0..2");
         NativeEngine eng;
-        fill_engine(eng, c, workers, w, alpha_bar);
+        fill_engine(eng, c, workers, w, alpha_bar, ckpt_cb);
         if ((mode == 1) != (eng.cfg.algo == 1))
           throw std::runtime_error(
               "native sync engine: mode/algo mismatch");
@@ -1277,5 +1534,7 @@ void register_native_engine(py::module_& m) {
           r = eng.run_sync(mode);
         }
         return result_dict(r);
-      });
+      },
+      py::arg("conf"), py::arg("workers"), py::arg("w"),
+      py::arg("alpha_bar"), py::arg("mode"), py::arg("ckpt_cb") = py::none());
 }
