@@ -8,6 +8,8 @@ framework's SGD history lives in ``Server.opt_vars``; this module is the
 LBFGS analog: a torch two-loop-recursion L-BFGS over the full-batch LSQ /
 logistic objective, recording ``(ms_since_start, w)`` every
 ``printer_freq`` iterations and exposing ``get_all_weights()``.
+The hinge objective is refused: it is non-smooth, and the line search and
+curvature pairs of L-BFGS assume a differentiable loss.
 
 Runs on CPU or GPU tensors (full-batch gradient = one GEMV per iteration —
 library territory, not a custom kernel)."""
@@ -57,6 +59,11 @@ class LBFGS:
                  objective: str = "lsq", l2: float = 0.0):
         if not (l2 >= 0.0 and l2 < float("inf")):
             raise ValueError(f"l2 must be finite and non-negative, got {l2!r}")
+        if objective not in ("lsq", "logistic"):
+            raise ValueError(
+                f"LBFGS supports the smooth objectives 'lsq' and 'logistic', "
+                f"got {objective!r} (hinge is non-smooth: train it with the "
+                f"SGD/SAGA engines)")
         self.l2 = float(l2)
         self.m = memory
         self.max_iter = max_iter

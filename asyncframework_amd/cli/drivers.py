@@ -5,7 +5,8 @@ Positional args (13) exactly as the reference drivers parse them
 [num rows] [num partitions] [num iterations] [step size] [taw] [batch rate]
 [bucket ratio] [printer freq] [coeff] [seed]; the MLlib baseline takes 8
 (SparkSGDMLLIB.scala:30-37). Extra engine flags (--device, --dtype,
---objective, --sparse, --history-placement) come after the positionals.
+--objective, --sparse, --history-placement, --test-file / --test-rows /
+--threshold for a held-out evaluation) come after the positionals.
 
 ``file name`` = 'synthetic' generates data of the given shape instead of
 loading a LibSVM file (no network in this environment).
@@ -44,7 +45,9 @@ def _engine_flags(p: argparse.ArgumentParser) -> None:
                    help="cpu | cuda | cuda:N (default cpu)")
     p.add_argument("--dtype", default="fp32",
                    choices=["fp32", "fp64", "bf16", "fp16"])
-    p.add_argument("--objective", default="lsq", choices=["lsq", "logistic"])
+    p.add_argument("--objective", default="lsq",
+                   choices=["lsq", "logistic", "hinge"],
+                   help="hinge = MLlib HingeGradient (linear SVM with --l2)")
     p.add_argument("--sparse", action="store_true",
                    help="CSR data path (rcv1-shape)")
     p.add_argument("--history-placement", default="device",
@@ -72,6 +75,16 @@ def _engine_flags(p: argparse.ArgumentParser) -> None:
     p.add_argument("--l1", type=float, default=0.0,
                    help="L1 penalty l1*||w||_1, applied as a soft-threshold "
                         "after the step (default 0)")
+    p.add_argument("--test-file", default="",
+                   help="held-out LibSVM file at [path name]+NAME, scored "
+                        "after the run (file inputs)")
+    p.add_argument("--test-rows", type=int, default=0,
+                   help="held-out rows drawn from the synthetic input's "
+                        "planted model with seed+1 (synthetic inputs)")
+    p.add_argument("--threshold", type=float, default=None,
+                   help="decision threshold of the held-out evaluation "
+                        "(default: 0 hinge, 0.5 lsq, probability 0.5 "
+                        "logistic)")
     p.add_argument("--resume-from", default="",
                    help="restore optimizer state from a checkpoint file "
                         "before running")
@@ -112,16 +125,39 @@ def _cfg13(a, algo: str, sync: bool) -> EngineConfig:
         checkpoint_every=a.checkpoint_every, l2=a.l2, l1=a.l1)
 
 
+def _load(cfg: EngineConfig, a, sparse: bool, device: str):
+    """(training data, held-out data or None) for the parsed flags."""
+    want_rows = a.test_rows > 0
+    data = runner.load_dataset(cfg, a.pathname, a.fname, sparse=sparse,
+                               device=device, return_w_true=want_rows)
+    if not (want_rows or a.test_file):
+        return data, None
+    w_true = None
+    if want_rows:
+        data, w_true = data
+    test = runner.load_test_dataset(cfg, a.pathname, test_file=a.test_file,
+                                    test_rows=a.test_rows, w_true=w_true,
+                                    sparse=sparse, device=device)
+    return data, test
+
+
+def _evaluate(cfg: EngineConfig, a, res, test_data, sparse: bool,
+              device: str) -> None:
+    if test_data is not None:
+        runner.evaluation_report(cfg, res, test_data, sparse, device=device,
+                                 threshold=a.threshold)
+
+
 def _run(cfg: EngineConfig, a, app: str, names, vals) -> None:
     import os
+    runner.check_test_flags(a.pathname, a.fname, a.test_file, a.test_rows)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world > 1:
         _run_dist(cfg, a, app, names, vals, world)
         return
     logfmt.print_header(app, names, vals)
     sparse = a.sparse
-    data = runner.load_dataset(cfg, a.pathname, a.fname, sparse=sparse,
-                               device=a.device)
+    data, test_data = _load(cfg, a, sparse, a.device)
     if sparse:
         workers = runner.build_csr_workers(cfg, *data)
     else:
@@ -129,6 +165,7 @@ def _run(cfg: EngineConfig, a, app: str, names, vals) -> None:
     res, _srv = runner.run_engine(cfg, workers, max_wall_s=a.max_wall_s,
                                   engine=a.engine, resume_from=a.resume_from)
     runner.final_report(cfg, res, data, sparse, device=a.device)
+    _evaluate(cfg, a, res, test_data, sparse, a.device)
 
 
 def _run_dist(cfg: EngineConfig, a, app: str, names, vals,
@@ -159,8 +196,7 @@ def _run_dist(cfg: EngineConfig, a, app: str, names, vals,
     if rank == 0:
         logfmt.print_header(app, names, vals)
     sparse = a.sparse
-    data = runner.load_dataset(cfg, a.pathname, a.fname, sparse=sparse,
-                               device="cpu")
+    data, test_data = _load(cfg, a, sparse, "cpu")
     shards = row_shards(cfg.N, cfg.num_workers)
     workers = []
     for j in range(M):
@@ -188,6 +224,7 @@ def _run_dist(cfg: EngineConfig, a, app: str, names, vals,
         res = eng.run(max_wall_s=a.max_wall_s, verbose=(rank == 0))
         if rank == 0:
             runner.final_report(cfg, res, data, sparse, device="cpu")
+            _evaluate(cfg, a, res, test_data, sparse, "cpu")
         dist.barrier()
         dist.destroy_process_group()
         return
@@ -204,6 +241,7 @@ def _run_dist(cfg: EngineConfig, a, app: str, names, vals,
                       resume_from=a.resume_from)
     if rank == 0:
         runner.final_report(cfg, res, data, sparse, device="cpu")
+        _evaluate(cfg, a, res, test_data, sparse, "cpu")
     dist.destroy_process_group()
 
 
@@ -256,14 +294,14 @@ def sgd_mllib(argv: Optional[List[str]] = None) -> None:
     import os
     vals = [a.pathname, a.fname, a.d, a.N, a.numPart, a.numIter, a.gamma,
             a.b]
+    runner.check_test_flags(a.pathname, a.fname, a.test_file, a.test_rows)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world > 1:
         a.resume_from = ""
         _run_dist(cfg, a, "MLlib SGD", ARG_NAMES_8, vals, world)
         return
     logfmt.print_header("MLlib SGD", ARG_NAMES_8, vals)
-    data = runner.load_dataset(cfg, a.pathname, a.fname, sparse=a.sparse,
-                               device=a.device)
+    data, test_data = _load(cfg, a, a.sparse, a.device)
     if a.sparse:
         workers = runner.build_csr_workers(cfg, *data)
     else:
@@ -271,3 +309,4 @@ def sgd_mllib(argv: Optional[List[str]] = None) -> None:
     res, _ = runner.run_engine(cfg, workers, max_wall_s=a.max_wall_s,
                                engine=a.engine)
     runner.final_report(cfg, res, data, a.sparse, device=a.device)
+    _evaluate(cfg, a, res, test_data, a.sparse, a.device)

@@ -14,6 +14,8 @@ from typing import Optional, Tuple
 import numpy as np
 import torch
 
+_LABEL_OBJECTIVES = ("logistic", "hinge")  # {0,1} labels
+
 SHAPES = {
     "mnist8m": (8_100_000, 784),
     "epsilon": (400_000, 2_000),
@@ -28,13 +30,18 @@ def synthetic_dense(n_rows: int, n_cols: int, *, seed: int = 42,
                     objective: str = "lsq",
                     w_true: Optional[torch.Tensor] = None,
                     noise: float = 0.01,
-                    chunk_rows: int = 1 << 20
-                    ) -> Tuple[torch.Tensor, torch.Tensor]:
+                    chunk_rows: int = 1 << 20,
+                    return_w_true: bool = False):
     """Dense (X, y) with a planted model so loss curves are meaningful.
 
-    X ~ N(0, 1/sqrt(d)); lsq: y = X w* + noise; logistic: y = Bernoulli-free
-    deterministic label sign(X w*) in {0,1} (keeps y reproducible across
-    devices). Generated chunk-wise on the target device."""
+    X ~ N(0, 1/sqrt(d)); lsq: y = X w* + noise; logistic and hinge:
+    y = Bernoulli-free deterministic label sign(X w*) in {0,1} (keeps y
+    reproducible across devices). Generated chunk-wise on the target device.
+
+    ``w_true`` plants a given model instead of drawing one (the draws that
+    follow are those of the default call minus that first one);
+    ``return_w_true`` returns (X, y, w_true) so a second call — another
+    seed, the same model — can make held-out rows."""
     dev = torch.device(device)
     gen = torch.Generator(device=dev)
     gen.manual_seed(seed)
@@ -49,24 +56,30 @@ def synthetic_dense(n_rows: int, n_cols: int, *, seed: int = 42,
         Xc = torch.randn((t - s, n_cols), generator=gen, device=dev,
                          dtype=torch.float32).mul_(scale)
         z = Xc @ w_true
-        if objective == "logistic":
+        if objective in _LABEL_OBJECTIVES:
             y[s:t] = (z > 0).float()
         else:
             if noise > 0:
                 z = z + noise * torch.randn(t - s, generator=gen, device=dev)
             y[s:t] = z
         X[s:t] = Xc.to(dtype)
+    if return_w_true:
+        return X, y, w_true
     return X, y
 
 
 def synthetic_csr(n_rows: int, n_cols: int, *, nnz_per_row: int = 73,
                   seed: int = 42, device: str | torch.device = "cpu",
                   objective: str = "lsq",
-                  dtype: torch.dtype = torch.float32
-                  ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+                  dtype: torch.dtype = torch.float32,
+                  w_true: Optional[np.ndarray] = None,
+                  return_w_true: bool = False):
     """Sparse CSR (indptr, indices, values, y), rcv1-like (~73 nnz/row,
     reference README datasets). Column draw is uniform; values N(0,1)/sqrt(nnz).
-    Built with numpy then moved to device."""
+    Built with numpy then moved to device. ``w_true`` (float32 [n_cols])
+    plants a given model — the default call's own draw is still made, so the
+    noise that follows it is unchanged; ``return_w_true`` returns
+    (indptr, indices, values, y, w_true) as for synthetic_dense."""
     rng = np.random.default_rng(seed)
     counts = np.maximum(1, rng.poisson(nnz_per_row, size=n_rows))
     indptr = np.zeros(n_rows + 1, dtype=np.int32)
@@ -79,16 +92,19 @@ def synthetic_csr(n_rows: int, n_cols: int, *, nnz_per_row: int = 73,
     order = np.lexsort((indices, rows))
     indices = indices[order]
     values = values[order]
-    w_true = rng.standard_normal(n_cols).astype(np.float32)
+    w_drawn = rng.standard_normal(n_cols).astype(np.float32)
+    w_true = (w_drawn if w_true is None
+              else np.asarray(w_true, dtype=np.float32))
     # y via sparse matvec
     z = np.zeros(n_rows, dtype=np.float64)
     np.add.at(z, rows, values.astype(np.float64) * w_true[indices])
-    if objective == "logistic":
+    if objective in _LABEL_OBJECTIVES:
         y = (z > 0).astype(np.float32)
     else:
         y = (z + 0.01 * rng.standard_normal(n_rows)).astype(np.float32)
     dev = torch.device(device)
-    return (torch.from_numpy(indptr).to(dev),
-            torch.from_numpy(indices).to(dev),
-            torch.from_numpy(values).to(dev).to(dtype),
-            torch.from_numpy(y).to(dev))
+    out = (torch.from_numpy(indptr).to(dev),
+           torch.from_numpy(indices).to(dev),
+           torch.from_numpy(values).to(dev).to(dtype),
+           torch.from_numpy(y).to(dev))
+    return out + (w_true,) if return_w_true else out

@@ -50,7 +50,9 @@ class EngineConfig:
     seed: int = 42
 
     # engine flags (new)
-    objective: str = "lsq"          # 'lsq' | 'logistic'
+    objective: str = "lsq"          # 'lsq' | 'logistic' | 'hinge' (MLlib
+                                    # HingeGradient: labels in {0,1},
+                                    # s = 2y-1, coefficient -s when 1 > s*z)
     algo: str = "asgd"              # 'asgd' | 'asaga'
     sync: bool = False
     dtype: str = "fp32"             # compute/storage dtype of X

@@ -73,7 +73,8 @@ class GraphEngine:
             self.alpha_bar = torch.zeros(d, dtype=torch.float32,
                                          device=device)
         self._graph: Optional[torch.cuda.CUDAGraph] = None
-        self._obj_code = {"lsq": 0, "logistic": 1}[cfg.objective]
+        self._obj_code = {"lsq": 0, "logistic": 1,
+                          "hinge": 2}[cfg.objective]  # csrc/link.h
         # dense path: per-block partial slabs + parallel reduce (no global
         # atomics — measured 9%-of-HBM cap with the atomic finalize)
         self.g_part = None

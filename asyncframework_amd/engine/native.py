@@ -33,7 +33,7 @@ import torch
 from .config import EngineConfig, check_penalties
 from .worker import Shard
 
-_OBJ = {"lsq": 0, "logistic": 1}
+_OBJ = {"lsq": 0, "logistic": 1, "hinge": 2}  # csrc/link.h
 _ALGO = {"asgd": 0, "asaga": 1}
 _SYNC_MODE = {"asgd": 0, "asaga": 1, "mllib": 2}
 

@@ -20,7 +20,7 @@ import torch
 from .config import EngineConfig, refuse_penalties
 from .worker import Shard
 
-_OBJ = {"lsq": 0, "logistic": 1}
+_OBJ = {"lsq": 0, "logistic": 1, "hinge": 2}  # csrc/link.h
 _ALGO = {"asgd": 0, "asaga": 1}
 
 

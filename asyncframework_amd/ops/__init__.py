@@ -9,8 +9,9 @@ torch fallback on GPU (debug only)."""
 
 from __future__ import annotations
 
+import math
 import os
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import numpy as np
 import torch
@@ -52,7 +53,7 @@ def _require_hip(op: str):
     return mod
 
 
-_OBJ_CODE = {"lsq": 0, "logistic": 1}
+_OBJ_CODE = {"lsq": 0, "logistic": 1, "hinge": 2}  # csrc/link.h
 
 
 def make_mask(device: torch.device, seed: int, round_k: int, row_start: int,
@@ -227,3 +228,103 @@ def objective_sweep_csr(indptr, indices, values, y, W, objective="lsq",
                         l1: float = 0.0) -> torch.Tensor:
     return torch_ref.objective_sweep_csr(indptr, indices, values, y, W,
                                          objective, N_total, l2=l2, l1=l1)
+
+
+class EvalResult(NamedTuple):
+    """Held-out score of T stacked iterates: ``loss`` fp64 [T] (loss_sum / N,
+    the normalisation of objective_sweep, no penalty term) and the confusion
+    counts int64 [T] at the decision threshold."""
+    loss: torch.Tensor
+    tp: torch.Tensor
+    fp: torch.Tensor
+    tn: torch.Tensor
+    fn: torch.Tensor
+
+    @property
+    def accuracy(self) -> torch.Tensor:
+        """(tp + tn) / rows, fp64 [T] (0 when there are no rows)."""
+        n = self.tp + self.fp + self.tn + self.fn
+        return (self.tp + self.tn).double() / n.clamp(min=1).double()
+
+
+def score_threshold(objective: str, threshold: Optional[float] = None
+                    ) -> float:
+    """The user's decision threshold as a threshold z_thr on the score
+    z = x.w, in fp64; a row is predicted positive iff z > z_thr.
+    hinge: z_thr = threshold, default 0 (MLlib SVMModel); lsq:
+    z_thr = threshold, default 0.5; logistic: threshold is a probability in
+    (0, 1), default 0.5, and z_thr = log(thr / (1 - thr)) — no sigmoid is
+    evaluated for the decision (LogisticRegressionModel)."""
+    if objective not in _OBJ_CODE:
+        raise ValueError(f"unknown objective {objective!r}")
+    if objective == "logistic":
+        thr = 0.5 if threshold is None else float(threshold)
+        if not 0.0 < thr < 1.0:
+            raise ValueError(
+                f"logistic threshold must lie in (0, 1), got {thr!r}")
+        return 0.0 if thr == 0.5 else math.log(thr / (1.0 - thr))
+    if threshold is None:
+        return 0.5 if objective == "lsq" else 0.0
+    thr = float(threshold)
+    if not math.isfinite(thr):
+        raise ValueError(f"threshold must be finite, got {thr!r}")
+    return thr
+
+
+def _eval_result(sums, n_rows: int, N_total: Optional[int]) -> EvalResult:
+    loss_sum, tp, fp, tn, fn = sums
+    N = N_total if N_total is not None else n_rows
+    return EvalResult(loss_sum / max(int(N), 1), tp, fp, tn, fn)
+
+
+def _eval_zeros(T: int, device) -> EvalResult:
+    z = lambda dt: torch.zeros(T, dtype=dt, device=device)
+    return EvalResult(z(torch.float64), *(z(torch.int64) for _ in range(4)))
+
+
+def evaluate(X: torch.Tensor, y: torch.Tensor, W: torch.Tensor,
+             objective: str = "lsq", *, threshold: Optional[float] = None,
+             N_total: Optional[int] = None) -> EvalResult:
+    """Score the stacked iterates W [T, d] on the rows (X, y) — typically
+    rows the model was not trained on — with the fused evaluation kernels
+    (K9): one pass over X per tile of iterates, nothing of size rows x T
+    written. w stays fp32 whatever X's dtype. CPU tensors take the fp64
+    reference."""
+    z_thr = score_threshold(objective, threshold)
+    if W.dim() != 2 or W.shape[1] != X.shape[1]:
+        raise ValueError(f"W must be [T, {X.shape[1]}], got {tuple(W.shape)}")
+    n_rows, T = X.shape[0], W.shape[0]
+    if n_rows == 0 or T == 0:
+        return _eval_zeros(T, X.device)
+    if X.is_cuda:
+        mod = _require_hip("evaluate")
+        if mod is not None:
+            return _eval_result(
+                mod.evaluate(X, y, W, _OBJ_CODE[objective], z_thr), n_rows,
+                N_total)
+    return _eval_result(torch_ref.evaluate(X, y, W, objective, z_thr),
+                        n_rows, N_total)
+
+
+def evaluate_csr(indptr: torch.Tensor, indices: torch.Tensor,
+                 values: torch.Tensor, y: torch.Tensor, W: torch.Tensor,
+                 objective: str = "lsq", *, threshold: Optional[float] = None,
+                 N_total: Optional[int] = None) -> EvalResult:
+    """CSR form of evaluate: one column gather per non-zero serves the
+    whole tile of iterates, and bf16 values are never expanded."""
+    z_thr = score_threshold(objective, threshold)
+    if W.dim() != 2:
+        raise ValueError(f"W must be [T, d], got {tuple(W.shape)}")
+    n_rows, T = indptr.shape[0] - 1, W.shape[0]
+    if n_rows <= 0 or T == 0:
+        return _eval_zeros(T, values.device)
+    if values.is_cuda:
+        mod = _require_hip("evaluate_csr")
+        if mod is not None:
+            return _eval_result(
+                mod.evaluate_csr(indptr, indices, values, y, W,
+                                 _OBJ_CODE[objective], z_thr), n_rows,
+                N_total)
+    return _eval_result(
+        torch_ref.evaluate_csr(indptr, indices, values, y, W, objective,
+                               z_thr), n_rows, N_total)

@@ -183,3 +183,57 @@ def saga_update(w, g, alpha_bar, gamma, inv_batch, inv_N, l2=0.0,
     _hip_core.saga_update(w.data_ptr(), g.data_ptr(), alpha_bar.data_ptr(),
                           gamma, inv_batch, inv_N, int(w.numel()), _stream(),
                           l2, l1)
+
+
+def _eval_buffers(W, d, device, grid, transposed):
+    """Zero-padded fp32 tiles of the iterates + the kernels' scratch and
+    output buffers. Returns (Wtiles, n_tiles, part_loss, part_cnt, out_loss,
+    out_cnt)."""
+    tt = _hip_core.eval_tile()
+    T = W.shape[0]
+    n_tiles = (T + tt - 1) // tt
+    Wp = torch.zeros(n_tiles * tt, d, dtype=torch.float32, device=device)
+    Wp[:T] = W.to(device=device, dtype=torch.float32)
+    if transposed:  # [n_tiles][d][tt]
+        Wp = Wp.view(n_tiles, tt, d).transpose(1, 2).contiguous()
+    part_loss = torch.empty(grid * tt, dtype=torch.float64, device=device)
+    part_cnt = torch.empty(grid * 4 * tt, dtype=torch.int64, device=device)
+    out_loss = torch.empty(n_tiles * tt, dtype=torch.float64, device=device)
+    out_cnt = torch.empty(4, n_tiles * tt, dtype=torch.int64, device=device)
+    return Wp, n_tiles, part_loss, part_cnt, out_loss, out_cnt
+
+
+def evaluate(X, y, W, obj, z_thr):
+    """(loss_sum, tp, fp, tn, fn) of the iterates W [T, d] over (X, y)."""
+    _chk(X, "X")
+    _chk(y, "y", torch.float32)
+    n_rows, d = X.shape
+    assert y.numel() == n_rows and W.shape[1] == d
+    assert n_rows < 2 ** 31, "row ids are 32-bit"
+    T = W.shape[0]
+    grid = _hip_core.eval_grid(n_rows, d, 0)
+    Wp, n_tiles, pl, pc, ol, oc = _eval_buffers(W, d, X.device, grid, False)
+    _hip_core.eval_dense(X.data_ptr(), y.data_ptr(), Wp.data_ptr(), n_tiles,
+                         n_rows, d, obj, float(z_thr), _xcode(X),
+                         pl.data_ptr(), pc.data_ptr(), ol.data_ptr(),
+                         oc.data_ptr(), _stream())
+    return (ol[:T], oc[0, :T], oc[1, :T], oc[2, :T], oc[3, :T])
+
+
+def evaluate_csr(indptr, indices, values, y, W, obj, z_thr):
+    _chk(indptr, "indptr", torch.int32)
+    _chk(indices, "indices", torch.int32)
+    _chk(values, "values")
+    _chk(y, "y", torch.float32)
+    n_rows = indptr.shape[0] - 1
+    assert y.numel() == n_rows
+    T, d = W.shape
+    grid = _hip_core.eval_grid(n_rows, d, 1)
+    Wp, n_tiles, pl, pc, ol, oc = _eval_buffers(W, d, values.device, grid,
+                                                True)
+    _hip_core.eval_csr(indptr.data_ptr(), indices.data_ptr(),
+                       values.data_ptr(), y.data_ptr(), Wp.data_ptr(),
+                       n_tiles, n_rows, d, obj, float(z_thr), _xcode(values),
+                       pl.data_ptr(), pc.data_ptr(), ol.data_ptr(),
+                       oc.data_ptr(), _stream())
+    return (ol[:T], oc[0, :T], oc[1, :T], oc[2, :T], oc[3, :T])

@@ -22,16 +22,45 @@ from typing import Optional, Tuple
 import torch
 
 
+OBJECTIVES = ("lsq", "logistic", "hinge")
+
+
+def _link(z: torch.Tensor, y: torch.Tensor, objective: str) -> torch.Tensor:
+    """Scalar gradient coefficient e from the score z = x.w and the label y
+    (csrc/link.h): z - y for 'lsq', sigmoid(z) - y for 'logistic'; 'hinge'
+    is MLlib's HingeGradient, labels in {0,1}, s = 2y - 1: e = -s when
+    1 > s*z (strict), else 0."""
+    y = y.float()
+    if objective == "lsq":
+        return z - y
+    elif objective == "logistic":
+        return torch.sigmoid(z) - y
+    elif objective == "hinge":
+        s = 2.0 * y - 1.0
+        return torch.where(1.0 > s * z, -s, torch.zeros_like(s))
+    raise ValueError(f"unknown objective {objective!r}")
+
+
+def _row_loss(Z: torch.Tensor, y: torch.Tensor, objective: str
+              ) -> torch.Tensor:
+    """Loss of every (row, iterate) score Z[i, t], in Z's dtype: (z - y)^2,
+    softplus(-s z) or max(0, 1 - s z), with s = 2y - 1."""
+    y = y.to(Z.dtype)[:, None]
+    if objective == "lsq":
+        return (Z - y) ** 2
+    zy = Z * (2.0 * y - 1.0)
+    if objective == "logistic":
+        return torch.nn.functional.softplus(-zy)
+    elif objective == "hinge":
+        return torch.clamp(1.0 - zy, min=0.0)
+    raise ValueError(f"unknown objective {objective!r}")
+
+
 def _residual(X: torch.Tensor, y: torch.Tensor, w: torch.Tensor,
               objective: str) -> torch.Tensor:
-    """Per-row scalar gradient coefficient e_i: x_i.w - y_i for 'lsq',
-    sigmoid(x_i.w) - y_i for 'logistic'."""
+    """Per-row scalar gradient coefficient e_i = _link(x_i.w, y_i)."""
     z = (X.to(w.dtype) @ w).float()
-    if objective == "lsq":
-        return z - y.float()
-    elif objective == "logistic":
-        return torch.sigmoid(z) - y.float()
-    raise ValueError(f"unknown objective {objective!r}")
+    return _link(z, y, objective)
 
 
 def grad_dense(X: torch.Tensor, y: torch.Tensor, w: torch.Tensor,
@@ -65,10 +94,7 @@ def grad_csr(indptr: torch.Tensor, indices: torch.Tensor, values: torch.Tensor,
         cols = indices[s:t].long()
         vals = values[s:t].float()
         z = torch.dot(vals, wf[cols])
-        if objective == "logistic":
-            e = torch.sigmoid(z) - y[i].float()
-        else:
-            e = z - y[i].float()
+        e = _link(z, y[i], objective)
         g.index_add_(0, cols, e * vals)
     return g, n
 
@@ -118,10 +144,7 @@ def saga_grad_csr(indptr: torch.Tensor, indices: torch.Tensor,
         cols = indices[s:t].long()
         vals = values[s:t].float()
         z = torch.dot(vals, wf[cols])
-        if objective == "logistic":
-            e = torch.sigmoid(z) - y[i].float()
-        else:
-            e = z - y[i].float()
+        e = _link(z, y[i], objective)
         e_out[j] = e
         g.index_add_(0, cols, (e - alpha[i].float()) * vals)
     return g, idx, e_out, n
@@ -134,7 +157,8 @@ def objective_sweep(X: torch.Tensor, y: torch.Tensor, W: torch.Tensor,
 
     W is [T, d] (stacked iterates — the reference computes all logged
     objectives in a single job, SparkASGDThread.scala:389-398). Returns [T]
-    fp64. lsq: sum((X w_t - y)^2)/N; logistic: mean log-loss. Non-zero
+    fp64. lsq: sum((X w_t - y)^2)/N; logistic: mean log-loss; hinge: mean
+    max(0, 1 - s z). Non-zero
     l2/l1 add ``penalty(W, objective, l2, l1)``."""
     T = W.shape[0]
     N = X.shape[0]
@@ -147,11 +171,7 @@ def objective_sweep(X: torch.Tensor, y: torch.Tensor, W: torch.Tensor,
         Xb = X[s:s + batch_rows]
         yb = y[s:s + batch_rows].float()
         Z = (Xb @ Wt.t()).float()  # [B, T] — library GEMM (MFMA on gfx950)
-        if objective == "lsq":
-            out += ((Z - yb[:, None]) ** 2).double().sum(dim=0)
-        else:
-            zy = Z * (2.0 * yb[:, None] - 1.0)
-            out += torch.nn.functional.softplus(-zy).double().sum(dim=0)
+        out += _row_loss(Z, yb, objective).double().sum(dim=0)
     out = out / N
     if l2 != 0.0 or l1 != 0.0:
         out = out + penalty(W, objective, l2, l1).to(out.device)
@@ -170,15 +190,53 @@ def objective_sweep_csr(indptr: torch.Tensor, indices: torch.Tensor,
                                  size=(n_rows, W.shape[1]))
     Z = torch.sparse.mm(sp, W.float().t())
     yb = y.float()
-    if objective == "lsq":
-        out = ((Z - yb[:, None]) ** 2).double().sum(dim=0)
-    else:
-        zy = Z * (2.0 * yb[:, None] - 1.0)
-        out = torch.nn.functional.softplus(-zy).double().sum(dim=0)
+    out = _row_loss(Z, yb, objective).double().sum(dim=0)
     out = out / N
     if l2 != 0.0 or l1 != 0.0:
         out = out + penalty(W, objective, l2, l1).to(out.device)
     return out
+
+
+def _confusion(Z: torch.Tensor, y: torch.Tensor, z_thr: float):
+    """tp, fp, tn, fn per column of Z: actual positive iff y > 0.5,
+    predicted positive iff z > z_thr."""
+    pos = (y > 0.5)[:, None]
+    pred = Z > z_thr
+    return ((pos & pred).sum(dim=0), (~pos & pred).sum(dim=0),
+            (~pos & ~pred).sum(dim=0), (pos & ~pred).sum(dim=0))
+
+
+def evaluate(X: torch.Tensor, y: torch.Tensor, W: torch.Tensor,
+             objective: str, z_thr: float, batch_rows: int = 65536):
+    """Reference of the fused evaluation kernels, in fp64 throughout:
+    (loss_sum fp64 [T], tp, fp, tn, fn int64 [T]) of the stacked iterates
+    W [T, d] over the rows of X. The row loss is _row_loss; the decision
+    is _confusion at the score threshold z_thr."""
+    T = W.shape[0]
+    loss = torch.zeros(T, dtype=torch.float64, device=X.device)
+    cnt = [torch.zeros(T, dtype=torch.int64, device=X.device)
+           for _ in range(4)]
+    Wd = W.to(X.device).double()
+    for s in range(0, X.shape[0], batch_rows):
+        yb = y[s:s + batch_rows].double()
+        Z = X[s:s + batch_rows].double() @ Wd.t()
+        loss += _row_loss(Z, yb, objective).sum(dim=0)
+        for c, part in zip(cnt, _confusion(Z, yb, z_thr)):
+            c += part
+    return (loss, *cnt)
+
+
+def evaluate_csr(indptr: torch.Tensor, indices: torch.Tensor,
+                 values: torch.Tensor, y: torch.Tensor, W: torch.Tensor,
+                 objective: str, z_thr: float):
+    """CSR form of evaluate (fp64 sparse product)."""
+    n_rows = indptr.shape[0] - 1
+    sp = torch.sparse_csr_tensor(indptr, indices, values.double(),
+                                 size=(n_rows, W.shape[1]))
+    Z = torch.sparse.mm(sp, W.to(values.device).double().t())
+    yb = y.double()
+    loss = _row_loss(Z, yb, objective).sum(dim=0)
+    return (loss, *_confusion(Z, yb, z_thr))
 
 
 def penalty(W: torch.Tensor, objective: str, l2: float,
@@ -186,8 +244,8 @@ def penalty(W: torch.Tensor, objective: str, l2: float,
     """Elastic-net term of the REPORTED objective, per stacked iterate, fp64:
     c*((l2/2)*||w_t||^2 + l1*||w_t||_1). c = 2 for lsq (the sweep's lsq value
     is sum((x.w-y)^2)/N, twice the (1/2)(.)^2 loss whose gradient the kernels
-    use), 1 for logistic — so the reported number is a constant multiple of
-    the minimised F."""
+    use), 1 for logistic and hinge — so the reported number is a constant
+    multiple of the minimised F."""
     c = 2.0 if objective == "lsq" else 1.0
     Wd = W.double()
     return c * (0.5 * float(l2) * (Wd * Wd).sum(dim=1)

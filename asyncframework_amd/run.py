@@ -22,23 +22,63 @@ from .engine.worker import Shard, Worker
 from .utils import logfmt
 
 
+def is_synthetic(pathname: str, fname: str) -> bool:
+    return fname.startswith("synthetic") or pathname.startswith("synthetic")
+
+
 def load_dataset(cfg: EngineConfig, pathname: str, fname: str,
-                 sparse: bool = False, device: str = "cpu"):
+                 sparse: bool = False, device: str = "cpu",
+                 return_w_true: bool = False):
     """'synthetic' fname -> generated data of (cfg.N, cfg.d); otherwise a
-    LibSVM file at pathname+fname (reference MLUtils.loadLibSVMFile)."""
+    LibSVM file at pathname+fname (reference MLUtils.loadLibSVMFile).
+    ``return_w_true`` (synthetic only) returns (data, w_true): the planted
+    model, for load_test_dataset."""
     dt = cfg.torch_dtype()
-    if fname.startswith("synthetic") or pathname.startswith("synthetic"):
-        if sparse:
-            return synthetic_csr(cfg.N, cfg.d, seed=cfg.seed, device=device,
-                                 objective=cfg.objective, dtype=dt)
-        return synthetic_dense(cfg.N, cfg.d, seed=cfg.seed, device=device,
-                               objective=cfg.objective, dtype=dt)
+    if is_synthetic(pathname, fname):
+        gen = synthetic_csr if sparse else synthetic_dense
+        out = gen(cfg.N, cfg.d, seed=cfg.seed, device=device,
+                  objective=cfg.objective, dtype=dt,
+                  return_w_true=return_w_true)
+        return (out[:-1], out[-1]) if return_w_true else out
+    assert not return_w_true, "a file input has no planted model"
     path = pathname + fname
     if sparse:
         return load_libsvm(path, n_features=cfg.d, dense=False, dtype=dt,
                            device=device)
     return load_libsvm(path, n_features=cfg.d, dense=True, dtype=dt,
                        device=device)
+
+
+def check_test_flags(pathname: str, fname: str, test_file: str,
+                     test_rows: int) -> None:
+    """--test-file belongs to a file input, --test-rows to a synthetic one,
+    and only one of them may be given."""
+    if test_file and test_rows:
+        raise ValueError("give --test-file or --test-rows, not both")
+    if test_rows < 0:
+        raise ValueError(f"--test-rows must be positive, got {test_rows}")
+    synth = is_synthetic(pathname, fname)
+    if test_file and synth:
+        raise ValueError("--test-file needs a file input; a synthetic input "
+                         "takes --test-rows")
+    if test_rows and not synth:
+        raise ValueError("--test-rows needs a synthetic input; a file input "
+                         "takes --test-file")
+
+
+def load_test_dataset(cfg: EngineConfig, pathname: str, *,
+                      test_file: str = "", test_rows: int = 0, w_true=None,
+                      sparse: bool = False, device: str = "cpu"):
+    """Held-out rows: a LibSVM file at pathname+test_file with cfg.d
+    features, or test_rows synthetic rows of the training set's planted
+    model ``w_true`` drawn with seed cfg.seed + 1."""
+    dt = cfg.torch_dtype()
+    if test_rows:
+        gen = synthetic_csr if sparse else synthetic_dense
+        return gen(test_rows, cfg.d, seed=cfg.seed + 1, device=device,
+                   objective=cfg.objective, dtype=dt, w_true=w_true)
+    return load_libsvm(pathname + test_file, n_features=cfg.d,
+                       dense=not sparse, dtype=dt, device=device)
 
 
 def build_dense_workers(cfg: EngineConfig, X: torch.Tensor, y: torch.Tensor,
@@ -153,3 +193,27 @@ def final_report(cfg: EngineConfig, res: RunResult, data, sparse: bool,
             (t_ms, float(o)) for (t_ms, _), o in zip(res.opt_vars, obj))
     else:
         logfmt.objective_lines([])
+
+
+def evaluation_report(cfg: EngineConfig, res: RunResult, test_data,
+                      sparse: bool, device: str = "cpu",
+                      threshold: Optional[float] = None) -> None:
+    """Held-out block after the epilogue: loss and accuracy of every logged
+    iterate on rows the run never trained on (ops.evaluate[_csr]: the fused
+    kernels on a GPU, the fp64 reference on the CPU)."""
+    y = test_data[-1]
+    n = int(y.shape[0])
+    if not res.opt_vars:
+        logfmt.evaluation_lines(n, [])
+        return
+    W = torch.stack([w for (_, w) in res.opt_vars]).to(device)
+    if sparse:
+        indptr, indices, values, y = test_data
+        ev = ops.evaluate_csr(indptr, indices, values, y, W, cfg.objective,
+                              threshold=threshold)
+    else:
+        X, y = test_data
+        ev = ops.evaluate(X, y, W, cfg.objective, threshold=threshold)
+    logfmt.evaluation_lines(
+        n, ((t_ms, float(l), float(a)) for (t_ms, _), l, a
+            in zip(res.opt_vars, ev.loss, ev.accuracy)))

@@ -52,3 +52,15 @@ def objective_lines(pairs: Iterable[Tuple[int, float]]) -> None:
     for t_ms, obj in pairs:
         print(f"{t_ms},{obj}")
     print("finished")
+
+
+def evaluation_lines(n_rows: int,
+                     triples: Iterable[Tuple[int, float, float]]) -> None:
+    """Held-out evaluation block, printed after ``finished``: the row count,
+    one ``time_ms,loss,accuracy`` line per logged iterate (Python float
+    repr), then ``evaluation finished``."""
+    print("*********************************")
+    print(f"Held-out rows: {n_rows}")
+    for t_ms, loss, acc in triples:
+        print(f"{t_ms},{loss},{acc}")
+    print("evaluation finished")

@@ -34,7 +34,8 @@ SOURCES = [ROOT / "csrc" / "kernels.hip", ROOT / "csrc" / "bindings.cpp",
            ROOT / "csrc" / "engine_resident.hip"]
 UPDATE_STEP = ROOT / "csrc" / "update_step.h"  # included by both extensions
 HEADERS = [ROOT / "csrc" / "philox.h", ROOT / "csrc" / "multi_update.h",
-           ROOT / "csrc" / "grad_wave.h", UPDATE_STEP]
+           ROOT / "csrc" / "grad_wave.h", ROOT / "csrc" / "link.h",
+           ROOT / "csrc" / "eval.h", UPDATE_STEP]
 DIST_SRC = ROOT / "csrc" / "server_dist.cpp"
 DIST_HIP = ROOT / "csrc" / "dist_update.hip"
 DIST_DIR = ROOT / "asyncframework_amd" / "_dist_build"

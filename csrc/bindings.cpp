@@ -65,6 +65,16 @@ void launch_saga_update_fused(float*, float*, float*, int*, float, float,
                               float, int, hipStream_t);
 int query_dense_kernel(int, int, int, int, int*);
 int query_update_kernel(int, int, int, int*);
+int query_eval_tile();
+int query_eval_grid(long, int, int);
+int query_eval_kernel(int, int*);
+int query_eval_kernel_count();
+void launch_eval_dense(const void*, const float*, const float*, int, long,
+                       int, int, double, int, double*, long long*, double*,
+                       long long*, hipStream_t);
+void launch_eval_csr(const int*, const int*, const void*, const float*,
+                     const float*, int, long, int, int, double, int, double*,
+                     long long*, double*, long long*, hipStream_t);
 void launch_multi_update(float*, float* const*, float* const*, float*, float,
                          float, float, int, const MultiUpdateArgs*, int,
                          float, float, hipStream_t);
@@ -360,6 +370,68 @@ PYBIND11_MODULE(_hip_core, m) {
                                   : "multi_update_kernel";
       name += std::string("<") + (((k >> 1) & 1) ? "true" : "false") + "," +
               ((k & 1) ? "true" : "false") + ">";
+      out[py::str(name)] = e;
+    }
+    return out;
+  });
+
+  // Fused evaluation (csrc/eval.h). W is n_tiles zero-padded tiles of
+  // [eval_tile()][d] fp32 (dense) or [d][eval_tile()] (CSR, transposed);
+  // part_* are per-block scratch sized by eval_grid(); out_loss is
+  // [n_tiles * tile] fp64 and out_cnt [4][n_tiles * tile] int64
+  // (tp, fp, tn, fn).
+  m.def("eval_tile", []() { return query_eval_tile(); });
+  m.def("eval_grid", [](long n_rows, int d, int csr) {
+    return query_eval_grid(n_rows, d, csr);
+  });
+  m.def("eval_dense",
+        [](uintptr_t X, uintptr_t y, uintptr_t W, int n_tiles, long n_rows,
+           int d, int objective, double z_thr, int x_is_bf16,
+           uintptr_t part_loss, uintptr_t part_cnt, uintptr_t out_loss,
+           uintptr_t out_cnt, uintptr_t stream) {
+          launch_eval_dense((const void*)X, (const float*)y, (const float*)W,
+                            n_tiles, n_rows, d, objective, z_thr, x_is_bf16,
+                            (double*)part_loss, (long long*)part_cnt,
+                            (double*)out_loss, (long long*)out_cnt,
+                            (hipStream_t)stream);
+          check(hipGetLastError(), "eval_dense launch");
+        });
+  m.def("eval_csr",
+        [](uintptr_t indptr, uintptr_t indices, uintptr_t values, uintptr_t y,
+           uintptr_t Wtt, int n_tiles, long n_rows, int d, int objective,
+           double z_thr, int v_is_bf16, uintptr_t part_loss,
+           uintptr_t part_cnt, uintptr_t out_loss, uintptr_t out_cnt,
+           uintptr_t stream) {
+          launch_eval_csr((const int*)indptr, (const int*)indices,
+                          (const void*)values, (const float*)y,
+                          (const float*)Wtt, n_tiles, n_rows, d, objective,
+                          z_thr, v_is_bf16, (double*)part_loss,
+                          (long long*)part_cnt, (double*)out_loss,
+                          (long long*)out_cnt, (hipStream_t)stream);
+          check(hipGetLastError(), "eval_csr launch");
+        });
+
+  // Compiled register / scratch / LDS use and blocks per CU of every
+  // evaluation-kernel instantiation, by name.
+  m.def("eval_kernel_info", []() {
+    py::dict out;
+    const int n = query_eval_kernel_count();
+    for (int k = 0; k < n; ++k) {
+      int v[7] = {0};
+      check((hipError_t)query_eval_kernel(k, v), "eval_kernel_info");
+      py::dict e;
+      e["num_regs"] = v[0];
+      e["local_size_bytes"] = v[1];
+      e["lds_bytes"] = v[2];
+      e["max_active_blocks_per_cu"] = v[3];
+      const std::string xt = v[5] ? "bf16" : "float";
+      std::string name;
+      if (v[4] == 0)
+        name = "eval_dense_kernel<" + xt + "," + std::to_string(v[6]) + ">";
+      else if (v[4] == 1)
+        name = "eval_dense_generic_kernel<" + xt + ">";
+      else
+        name = "eval_csr_kernel<" + xt + "," + std::to_string(v[6]) + ">";
       out[py::str(name)] = e;
     }
     return out;

@@ -221,7 +221,7 @@ struct EngineCfg {
   long taw = 1 << 30;
   uint64_t seed = 42;
   int algo = 0;       // 0 asgd, 1 asaga
-  int objective = 0;  // 0 lsq, 1 logistic
+  int objective = 0;  // 0 lsq, 1 logistic, 2 hinge (link.h)
   double coeff = 0.0; // delay model
   long calib_window = 0;
   long mark_lo = -1, mark_hi = -1;

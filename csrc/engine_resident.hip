@@ -40,6 +40,7 @@
 #include <cstdint>
 #include <cstdio>
 
+#include "link.h"
 #include "philox.h"
 
 #define RES_BLOCK 256
@@ -78,7 +79,7 @@ struct ResidentArgs {
   int gate;
   int x_is_bf16;
   int algo;                 // 0 asgd, 1 asaga
-  int objective;            // 0 lsq, 1 logistic
+  int objective;            // 0 lsq, 1 logistic, 2 hinge (link.h)
   double coeff;             // straggler model (0 off, -1 cloud, >0 worker 0)
   long long calib_window;
   double cycles_per_ms;
@@ -271,11 +272,7 @@ __device__ void worker_round(const ResidentArgs& a, int w, int b,
           continue;
         }
         const int r = rows_s[i0 + u * WAVES];
-        float e;
-        if (a.objective == 1)
-          e = 1.f / (1.f + __expf(-pu)) - y[r];
-        else
-          e = pu - y[r];
+        const float e = link_residual_rt(pu, y[r], a.objective);
         scale[u] = e;
         if (a.algo == 1) {
           // SAGA: corrected gradient (e - alpha_r) * x, new scalar = e

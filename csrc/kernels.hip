@@ -24,6 +24,10 @@
 //                        batched (multi_update), sync-round, fused-graph and
 //                        reduce+update kernels all call it.
 //   K8 philox.h        — in-kernel counter-based Bernoulli mask.
+//   K9 eval.h          — fused held-out evaluation: loss sum + confusion
+//                        counts of a tile of stacked iterates in one pass
+//                        over the rows (included at the end of this file).
+// The link function of K1-K3 (lsq / logistic / hinge) lives in link.h.
 // Launchers: runtime (dtype, saga, ITERS, DEPTH, LPR, flags) become template
 // arguments through with_const / with_bool / with_xt_saga / with_pipe_shape.
 //
@@ -60,6 +64,7 @@
 #include <type_traits>
 #include "philox.h"
 #include "grad_wave.h"
+#include "link.h"
 #include "update_step.h"
 
 #define WAVE 64
@@ -104,11 +109,6 @@ __device__ __forceinline__ void publish_done(
   }
 }
 
-__device__ __forceinline__ float link_residual(float z, float yv, int obj) {
-  if (obj == 1) return 1.0f / (1.0f + __expf(-z)) - yv;  // logistic
-  return z - yv;                                         // lsq
-}
-
 template <typename XT>
 __device__ __forceinline__ float to_f32(XT v);
 template <>
@@ -143,7 +143,7 @@ __device__ __forceinline__ void load4<__hip_bfloat16>(
 
 // LPR = lanes per row (64, 32 or 16): rows are processed by aligned
 // sub-waves so 64/LPR rows are in flight per wave.
-template <typename XT, bool SAGA, int LPR>
+template <typename XT, bool SAGA, int LPR, bool HINGE>
 __global__ __launch_bounds__(BLOCK) void grad_dense_kernel(
     const XT* __restrict__ X, const float* __restrict__ y,
     const float* __restrict__ w, float* __restrict__ g_out,
@@ -214,7 +214,7 @@ __global__ __launch_bounds__(BLOCK) void grad_dense_kernel(
 #pragma unroll
         for (int off = LPR / 2; off > 0; off >>= 1)
           z += __shfl_xor(z, off, WAVE);
-        float e = link_residual(z, y[rr], objective);
+        float e = link_residual<HINGE>(z, y[rr], objective);
         float coeff = e;
         if (SAGA) {
           const float a_old = alpha[rr];
@@ -607,7 +607,7 @@ __global__ void bump_counter_kernel(int* __restrict__ p) { *p += 1; }
 // globally compacted (rowlist, ylist) produced by scan_rows_kernel. Each
 // block stages its contiguous slice into LDS first (per-row ordinary
 // global loads inside the pipeline would reintroduce the vmcnt(0) drains).
-template <typename XT, int PBLOCK, int DEPTH, int ITERS>
+template <typename XT, int PBLOCK, int DEPTH, int ITERS, bool HINGE>
 __global__ __launch_bounds__(PBLOCK) void grad_dense_list_kernel(
     const XT* __restrict__ X, const float* __restrict__ w,
     float* __restrict__ g_part, const int* __restrict__ rowlist,
@@ -644,7 +644,9 @@ __global__ __launch_bounds__(PBLOCK) void grad_dense_list_kernel(
     __syncthreads();
     pipe_drain<XT, NW, DEPTH, ITERS>(
         X, total_elems, d, rowq, nq, w_lds, gw, wave, lane,
-        [&](int q, float z) { return link_residual(z, yq[q], objective); });
+        [&](int q, float z) {
+          return link_residual<HINGE>(z, yq[q], objective);
+        });
   }
   __syncthreads();
   flush_partials<PBLOCK, NW, DPAD>(gacc, g_part, d, gridDim.x, blockIdx.x);
@@ -652,7 +654,8 @@ __global__ __launch_bounds__(PBLOCK) void grad_dense_list_kernel(
 
 // __forceinline__ is load-bearing: left out of line, the body inherits no
 // launch bounds from its kernels and takes the whole register file.
-template <typename XT, bool SAGA, int PBLOCK, int DEPTH, int ITERS>
+template <typename XT, bool SAGA, int PBLOCK, int DEPTH, int ITERS,
+          bool HINGE>
 __device__ __forceinline__ void grad_dense_pipe_body(
     const XT* __restrict__ X, const float* __restrict__ y,
     const float* __restrict__ w, float* __restrict__ g_out,
@@ -712,7 +715,7 @@ __device__ __forceinline__ void grad_dense_pipe_body(
     local_count += pipe_drain<XT, NW, DEPTH, ITERS>(
         X, total_elems, d, rowq, nq, w_lds, gw, wave, lane,
         [&](int q, float z) {
-          const float e = link_residual(z, yq[q], objective);
+          const float e = link_residual<HINGE>(z, yq[q], objective);
           if (!SAGA) return e;
           const float coeff = e - aq[q];
           if (lane == 0) eq[q] = e;  // committed after the barrier
@@ -755,7 +758,8 @@ __device__ __forceinline__ void grad_dense_pipe_body(
   publish_done(done_flag, done_val, done_arr, nblk);
 }
 
-template <typename XT, bool SAGA, int PBLOCK, int DEPTH, int ITERS>
+template <typename XT, bool SAGA, int PBLOCK, int DEPTH, int ITERS,
+          bool HINGE>
 __global__
 __launch_bounds__(PBLOCK, (PipeShape<XT, SAGA, DEPTH, ITERS>::HINT))
 void grad_dense_pipe_kernel(
@@ -768,7 +772,7 @@ void grad_dense_pipe_kernel(
     uint64_t seed, uint32_t round_k, uint64_t row_start, uint32_t threshold,
     int take_all, int objective, unsigned long long* done_flag,
     unsigned long long done_val, unsigned long long* done_arr) {
-  grad_dense_pipe_body<XT, SAGA, PBLOCK, DEPTH, ITERS>(
+  grad_dense_pipe_body<XT, SAGA, PBLOCK, DEPTH, ITERS, HINGE>(
       X, y, w, g_out, g_part, n_out, alpha, idx_out, e_out, pos_ctr, k_dev,
       commit_now, n_rows, d, seed, round_k, row_start, threshold, take_all,
       objective, done_flag, done_val, done_arr, blockIdx.x, gridDim.x);
@@ -782,7 +786,8 @@ void grad_dense_pipe_kernel(
 // kernels. Per-worker invariants (X, y, wbuf, g, n_rows, flags) live in a
 // device table built once at engine init; the per-round variables (slot
 // list, Philox round keys, serials) travel by value in the launch args.
-template <typename XT, bool SAGA, int PBLOCK, int DEPTH, int ITERS>
+template <typename XT, bool SAGA, int PBLOCK, int DEPTH, int ITERS,
+          bool HINGE>
 __global__
 __launch_bounds__(PBLOCK, (PipeShape<XT, SAGA, DEPTH, ITERS>::HINT))
 void grad_dense_wave_kernel(
@@ -793,7 +798,7 @@ void grad_dense_wave_kernel(
   const int bid = cmd.interleave ? (int)(blockIdx.x / cmd.n)
                                  : (int)(blockIdx.x % cmd.bper);
   const GradWaveSlot sl = slots[cmd.wid[si]];
-  grad_dense_pipe_body<XT, SAGA, PBLOCK, DEPTH, ITERS>(
+  grad_dense_pipe_body<XT, SAGA, PBLOCK, DEPTH, ITERS, HINGE>(
       (const XT*)sl.X, sl.y, sl.wbuf, sl.g, nullptr, sl.n_out, sl.alpha,
       sl.idx_out, sl.e_out, sl.pos_ctr, nullptr, 0, sl.n_rows, d, seed,
       cmd.round_k[si], (uint64_t)sl.row_start, threshold, take_all,
@@ -837,7 +842,7 @@ __global__ __launch_bounds__(BLOCK) void reduce_partials_kernel(
 // wastes most of the wave; 16-lane sub-waves keep 4 rows in flight per
 // wave (the gradient scatter uses global atomics — no LDS slabs — so
 // unlike the dense kernel, sub-waves here cost no occupancy).
-template <typename VT, bool SAGA, int LPR>
+template <typename VT, bool SAGA, int LPR, bool HINGE>
 __device__ void grad_csr_body(
     const int* __restrict__ indptr, const int* __restrict__ indices,
     const VT* __restrict__ values, const float* __restrict__ y,
@@ -886,7 +891,7 @@ __device__ void grad_csr_body(
 #pragma unroll
         for (int off = LPR / 2; off > 0; off >>= 1)
           z += __shfl_xor(z, off, WAVE);
-        float e = link_residual(z, y[rr], objective);
+        float e = link_residual<HINGE>(z, y[rr], objective);
         float coeff = e;
         if (SAGA) {
           const float a_old = alpha[rr];
@@ -919,7 +924,7 @@ __device__ void grad_csr_body(
   publish_done(done_flag, done_val, done_arr, nblk);
 }
 
-template <typename VT, bool SAGA, int LPR>
+template <typename VT, bool SAGA, int LPR, bool HINGE>
 __global__ __launch_bounds__(BLOCK) void grad_csr_kernel(
     const int* __restrict__ indptr, const int* __restrict__ indices,
     const VT* __restrict__ values, const float* __restrict__ y,
@@ -931,15 +936,15 @@ __global__ __launch_bounds__(BLOCK) void grad_csr_kernel(
     uint64_t row_start, uint32_t threshold, int take_all, int objective,
     unsigned long long* done_flag, unsigned long long done_val,
     unsigned long long* done_arr) {
-  grad_csr_body<VT, SAGA, LPR>(indptr, indices, values, y, w, g_out, n_out,
-                               alpha, idx_out, e_out, pos_ctr, k_dev,
-                               commit_now, n_rows, seed, round_k, row_start,
-                               threshold, take_all, objective, done_flag,
-                               done_val, done_arr, blockIdx.x, gridDim.x);
+  grad_csr_body<VT, SAGA, LPR, HINGE>(
+      indptr, indices, values, y, w, g_out, n_out, alpha, idx_out, e_out,
+      pos_ctr, k_dev, commit_now, n_rows, seed, round_k, row_start, threshold,
+      take_all, objective, done_flag, done_val, done_arr, blockIdx.x,
+      gridDim.x);
 }
 
 // CSR wave: one kernel per quorum wave (see grad_dense_wave_kernel)
-template <typename VT, bool SAGA, int LPR>
+template <typename VT, bool SAGA, int LPR, bool HINGE>
 __global__ __launch_bounds__(BLOCK) void grad_csr_wave_kernel(
     const CsrWaveSlot* __restrict__ slots, GradWaveCmd cmd, uint64_t seed,
     uint32_t threshold, int take_all, int objective) {
@@ -948,7 +953,7 @@ __global__ __launch_bounds__(BLOCK) void grad_csr_wave_kernel(
   const int bid = cmd.interleave ? (int)(blockIdx.x / cmd.n)
                                  : (int)(blockIdx.x % cmd.bper);
   const CsrWaveSlot sl = slots[cmd.wid[si]];
-  grad_csr_body<VT, SAGA, LPR>(
+  grad_csr_body<VT, SAGA, LPR, HINGE>(
       sl.indptr, sl.indices, (const VT*)sl.values, sl.y, sl.wbuf, sl.g,
       sl.n_out, sl.alpha, sl.idx_out, sl.e_out, sl.pos_ctr, nullptr, 0,
       sl.n_rows, seed, cmd.round_k[si], (uint64_t)sl.row_start, threshold,
@@ -1437,6 +1442,14 @@ static void with_xt_saga(int is_bf16, int saga, F&& f) {
     else f(float{}, SG);
   });
 }
+// the gradient launchers' form: + bool_constant<objective is hinge>, the
+// kernels' HINGE argument (link.h)
+template <typename F>
+static void with_xt_saga_obj(int is_bf16, int saga, int objective, F&& f) {
+  with_xt_saga(is_bf16, saga, [&](auto xt, auto SG) {
+    with_bool(objective == 2, [&](auto HG) { f(xt, SG, HG); });
+  });
+}
 
 // f(integral_constant<ITERS>, integral_constant<DEPTH>) for the runtime
 // (iters, depth) pair: the one switch over the instantiated shapes.
@@ -1470,14 +1483,16 @@ static void launch_dense(const void* X, const float* y, const float* w,
   const int grid = grad_grid(n_rows);
   const char* np = std::getenv("ASYNCAMD_NO_PIPE");
   const bool pipe_ok = (d % 4 == 0) && (d <= 2048) && !(np && np[0] == '1');
-  with_xt_saga(x_is_bf16, saga, [&](auto xt, auto sg) {
+  with_xt_saga_obj(x_is_bf16, saga, objective, [&](auto xt, auto sg,
+                                                   auto hg) {
     using XT = decltype(xt);
     constexpr bool SG = decltype(sg)::value;
+    constexpr bool HG = decltype(hg)::value;
     if (pipe_ok) {
       const int iters = pipe_iters(d);
       with_pipe_shape(iters, pipe_depth(iters, false), [&](auto IT, auto DP) {
         constexpr int it = decltype(IT)::value, dp = decltype(DP)::value;
-        hipLaunchKernelGGL((grad_dense_pipe_kernel<XT, SG, 256, dp, it>),
+        hipLaunchKernelGGL((grad_dense_pipe_kernel<XT, SG, 256, dp, it, HG>),
                            dim3(grid), dim3(256),
                            (PipeShape<XT, SG, dp, it>::LDS), stream,
                            (const XT*)X, y, w, g_out, g_part, n_out, alpha,
@@ -1491,7 +1506,7 @@ static void launch_dense(const void* X, const float* y, const float* w,
     const int lpr = pick_lpr(d);
     const size_t smem = (size_t)(1 + 4 * (WAVE / lpr)) * d * sizeof(float);
     with_const<16, 32, 64>(lpr, [&](auto L) {
-      hipLaunchKernelGGL((grad_dense_kernel<XT, SG, decltype(L)::value>),
+      hipLaunchKernelGGL((grad_dense_kernel<XT, SG, decltype(L)::value, HG>),
                          dim3(grid), dim3(BLOCK), smem, stream, (const XT*)X,
                          y, w, g_out, g_part, n_out, alpha, idx_out, e_out,
                          pos_ctr, k_dev, commit_now, n_rows, d, seed, round_k,
@@ -1515,11 +1530,13 @@ static void launch_csr(const int* indptr, const int* indices,
   const uint32_t thr = philox_threshold(rate);
   const int take_all = rate >= 1.0;
   const int grid = grad_grid(n_rows);
-  with_xt_saga(v_is_bf16, saga, [&](auto vt, auto sg) {
+  with_xt_saga_obj(v_is_bf16, saga, objective, [&](auto vt, auto sg,
+                                                   auto hg) {
     using VT = decltype(vt);
+    constexpr bool HG = decltype(hg)::value;
     with_const<8, 32, 64, 16>(csr_lpr(), [&](auto L) {
       hipLaunchKernelGGL(
-          (grad_csr_kernel<VT, decltype(sg)::value, decltype(L)::value>),
+          (grad_csr_kernel<VT, decltype(sg)::value, decltype(L)::value, HG>),
           dim3(grid), dim3(BLOCK), 0, stream, indptr, indices,
           (const VT*)values, y, w, g_out, n_out, alpha, idx_out, e_out,
           pos_ctr, k_dev, commit_now, n_rows, seed, round_k, row_start, thr,
@@ -1555,11 +1572,12 @@ void launch_grad_dense_list(const void* X, const float* w, float* g_part,
                             hipStream_t stream) {
   const int grid = grad_grid(n_rows);
   const int iters = pipe_iters(d);
-  with_xt_saga(x_is_bf16, 0, [&](auto xt, auto) {
+  with_xt_saga_obj(x_is_bf16, 0, objective, [&](auto xt, auto, auto hg) {
     using XT = decltype(xt);
+    constexpr bool HG = decltype(hg)::value;
     with_pipe_shape(iters, pipe_depth(iters, false), [&](auto IT, auto DP) {
       constexpr int it = decltype(IT)::value, dp = decltype(DP)::value;
-      hipLaunchKernelGGL((grad_dense_list_kernel<XT, 256, dp, it>),
+      hipLaunchKernelGGL((grad_dense_list_kernel<XT, 256, dp, it, HG>),
                          dim3(grid), dim3(256), list_lds_bytes(it), stream,
                          (const XT*)X, w, g_part, rowlist, ylist, count_dev,
                          n_rows, d, objective);
@@ -1629,12 +1647,14 @@ void launch_grad_dense_wave(const void* slots_dev, const void* cmd_host,
   const int grid = cmd->n * cmd->bper;
   const int iters = pipe_iters(d);
   (void)max_rows;
-  with_xt_saga(x_is_bf16, saga, [&](auto xt, auto sg) {
+  with_xt_saga_obj(x_is_bf16, saga, objective, [&](auto xt, auto sg,
+                                                   auto hg) {
     using XT = decltype(xt);
     constexpr bool SG = decltype(sg)::value;
+    constexpr bool HG = decltype(hg)::value;
     with_pipe_shape(iters, pipe_depth(iters, true), [&](auto IT, auto DP) {
       constexpr int it = decltype(IT)::value, dp = decltype(DP)::value;
-      hipLaunchKernelGGL((grad_dense_wave_kernel<XT, SG, 256, dp, it>),
+      hipLaunchKernelGGL((grad_dense_wave_kernel<XT, SG, 256, dp, it, HG>),
                          dim3(grid), dim3(256),
                          (PipeShape<XT, SG, dp, it>::LDS), stream,
                          (const GradWaveSlot*)slots_dev, *cmd, d, seed, thr,
@@ -1647,8 +1667,9 @@ void launch_grad_dense_wave(const void* slots_dev, const void* cmd_host,
 // out = {iters, depth, occupancy hint, numRegs, localSizeBytes (scratch),
 // dynamic LDS bytes, max active 256-thread blocks per CU with that LDS, 0}.
 // wave = 1 describes grad_dense_wave_kernel, 0 the solo
-// grad_dense_pipe_kernel. Returns 0, a hipError_t, or -1 when d is not
-// served by the pipelined kernels.
+// grad_dense_pipe_kernel (the lsq / logistic instantiation, HINGE = false).
+// Returns 0, a hipError_t, or -1 when d is not served by the pipelined
+// kernels.
 int query_dense_kernel(int d, int x_is_bf16, int saga, int wave, int* out) {
   if (d <= 0 || d % 4 != 0 || d > 2048) return -1;
   const int iters = pipe_iters(d);
@@ -1661,8 +1682,10 @@ int query_dense_kernel(int d, int x_is_bf16, int saga, int wave, int* out) {
       constexpr int it = decltype(IT)::value, dp = decltype(DP)::value;
       using Shape = PipeShape<XT, SG, dp, it>;
       const void* fn =
-          wave ? (const void*)grad_dense_wave_kernel<XT, SG, 256, dp, it>
-               : (const void*)grad_dense_pipe_kernel<XT, SG, 256, dp, it>;
+          wave ? (const void*)
+                     grad_dense_wave_kernel<XT, SG, 256, dp, it, false>
+               : (const void*)
+                     grad_dense_pipe_kernel<XT, SG, 256, dp, it, false>;
       hipFuncAttributes attr;
       hipError_t e = hipFuncGetAttributes(&attr, fn);
       int nb = 0;
@@ -1764,11 +1787,13 @@ void launch_grad_csr_wave(const void* slots_dev, const void* cmd_host,
   const uint32_t thr = philox_threshold(rate);
   const int take_all = rate >= 1.0;
   const int grid = cmd->n * cmd->bper;
-  with_xt_saga(v_is_bf16, saga, [&](auto vt, auto sg) {
+  with_xt_saga_obj(v_is_bf16, saga, objective, [&](auto vt, auto sg,
+                                                   auto hg) {
+    constexpr bool HG = decltype(hg)::value;
     with_const<8, 32, 64, 16>(csr_lpr(), [&](auto L) {
       hipLaunchKernelGGL((grad_csr_wave_kernel<decltype(vt),
                                                decltype(sg)::value,
-                                               decltype(L)::value>),
+                                               decltype(L)::value, HG>),
                          dim3(grid), dim3(BLOCK), 0, stream,
                          (const CsrWaveSlot*)slots_dev, *cmd, seed, thr,
                          take_all, objective);
@@ -1929,3 +1954,8 @@ void launch_alpha_gather(float* a_dst, const float* a_src, const int* rows,
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------- K9
+// Fused held-out evaluation kernels and their launchers: built on the row
+// machinery (RowVec, row_rsrc, cvt4, to_f32) and the with_const helper above.
+#include "eval.h"
