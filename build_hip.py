@@ -32,10 +32,6 @@ SOURCES = [ROOT / "csrc" / "kernels.hip", ROOT / "csrc" / "bindings.cpp",
            ROOT / "csrc" / "libsvm_parser.cpp",
            ROOT / "csrc" / "engine_native.cpp",
            ROOT / "csrc" / "engine_resident.hip"]
-UPDATE_STEP = ROOT / "csrc" / "update_step.h"  # included by both extensions
-HEADERS = [ROOT / "csrc" / "philox.h", ROOT / "csrc" / "multi_update.h",
-           ROOT / "csrc" / "grad_wave.h", ROOT / "csrc" / "link.h",
-           ROOT / "csrc" / "eval.h", UPDATE_STEP]
 DIST_SRC = ROOT / "csrc" / "server_dist.cpp"
 DIST_HIP = ROOT / "csrc" / "dist_update.hip"
 DIST_DIR = ROOT / "asyncframework_amd" / "_dist_build"
@@ -47,23 +43,29 @@ def so_path() -> Path:
     return ROOT / "asyncframework_amd" / f"_hip_core{suffix}"
 
 
-def src_hash() -> str:
-    """sha256 over the _hip_core sources + target arch (hex, 16 chars)."""
+def headers() -> list:
+    """Every csrc header. Both extensions hash all of them: which one
+    includes which is not tracked, and a header edit that failed to force a
+    rebuild is the stale-binary failure this file exists to prevent."""
+    return sorted((ROOT / "csrc").glob("*.h"))
+
+
+def _hash(files) -> str:
     h = hashlib.sha256()
     h.update(ARCH.encode())
-    for s in sorted(SOURCES + HEADERS):
+    for s in sorted(files):
         h.update(s.name.encode())
         h.update(s.read_bytes())
     return h.hexdigest()[:16]
 
 
+def src_hash() -> str:
+    """sha256 over the _hip_core sources + target arch (hex, 16 chars)."""
+    return _hash(SOURCES + headers())
+
+
 def dist_src_hash() -> str:
-    h = hashlib.sha256()
-    h.update(ARCH.encode())
-    h.update(DIST_SRC.read_bytes())
-    h.update(DIST_HIP.read_bytes())
-    h.update(UPDATE_STEP.read_bytes())
-    return h.hexdigest()[:16]
+    return _hash([DIST_SRC, DIST_HIP] + headers())
 
 
 def _read_prov() -> dict:

@@ -18,6 +18,7 @@
 #include <string>
 #include <vector>
 
+#include "launchers.h"
 #include "multi_update.h"
 
 namespace py = pybind11;
@@ -25,60 +26,6 @@ namespace py = pybind11;
 void register_libsvm(py::module_& m);  // csrc/libsvm_parser.cpp
 void register_native_engine(py::module_& m);  // csrc/engine_native.cpp
 void register_resident_engine(py::module_& m);  // csrc/engine_resident.hip
-
-extern "C" {
-void launch_grad_dense(const void*, const float*, const float*, float*,
-                       float*, int*, const int*, long, int, uint64_t,
-                       uint32_t, uint64_t, double, int, int, hipStream_t);
-void launch_saga_grad_dense(const void*, const float*, const float*, float*,
-                            float*, float*, int*, int*, float*, int*,
-                            const int*, int, long, int, uint64_t, uint32_t,
-                            uint64_t, double, int, int, hipStream_t);
-int query_grad_grid(long);
-void launch_reduce_partials(const float*, float*, int, int, int,
-                            hipStream_t);
-void launch_scan_rows(const float*, int*, float*, int*, const int*, long,
-                      uint64_t, uint32_t, uint64_t, double, hipStream_t);
-void launch_bump_counter(int*, hipStream_t);
-void launch_grad_dense_list(const void*, const float*, float*, const int*,
-                            const float*, const int*, long, int, int, int,
-                            hipStream_t);
-void launch_sgd_reduce_update(const float*, float*, int*, int*, float, float,
-                              int, int, int, int, hipStream_t);
-void launch_grad_csr(const int*, const int*, const void*, const float*,
-                     const float*, float*, int*, const int*, long, uint64_t,
-                     uint32_t, uint64_t, double, int, int, hipStream_t);
-void launch_saga_grad_csr(const int*, const int*, const void*, const float*,
-                          const float*, float*, float*, int*, int*, float*,
-                          int*, const int*, int, long, uint64_t, uint32_t,
-                          uint64_t, double, int, int, hipStream_t);
-void launch_sgd_update(float*, const float*, float, float, int, float, float,
-                       hipStream_t);
-void launch_saga_update(float*, const float*, float*, float, float, float,
-                        int, float, float, hipStream_t);
-void launch_saga_commit(float*, const int*, const float*, int, hipStream_t);
-void launch_alpha_gather(float*, const float*, const int*, const int*, int,
-                         hipStream_t);
-void launch_sgd_update_fused(float*, float*, int*, float, float, int, int,
-                             hipStream_t);
-void launch_saga_update_fused(float*, float*, float*, int*, float, float,
-                              float, int, hipStream_t);
-int query_dense_kernel(int, int, int, int, int*);
-int query_update_kernel(int, int, int, int*);
-int query_eval_tile();
-int query_eval_grid(long, int, int);
-int query_eval_kernel(int, int*);
-int query_eval_kernel_count();
-void launch_eval_dense(const void*, const float*, const float*, int, long,
-                       int, int, double, int, double*, long long*, double*,
-                       long long*, hipStream_t);
-void launch_eval_csr(const int*, const int*, const void*, const float*,
-                     const float*, int, long, int, int, double, int, double*,
-                     long long*, double*, long long*, hipStream_t);
-void launch_multi_update(float*, float* const*, float* const*, float*, float,
-                         float, float, int, const MultiUpdateArgs*, int,
-                         float, float, hipStream_t);
-}
 
 static void check(hipError_t err, const char* what) {
   if (err != hipSuccess)

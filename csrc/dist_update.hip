@@ -5,6 +5,7 @@
 // update_step.h, which this separately built extension includes too.
 
 #include <hip/hip_runtime.h>
+#include "dist_launchers.h"  // checks the two definitions below
 #include "update_step.h"
 
 namespace {

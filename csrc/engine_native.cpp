@@ -21,7 +21,8 @@
 //   accept:      tau filter; accepted gradients accumulate into ONE
 //                elementwise-sequential multi-update kernel per sweep;
 //                requeue; quorum-gated redispatch;
-//   delay:       the reference's straggler model (cloud long-tail / coeff),
+//   delay:       the reference's straggler model (cloud long-tail / coeff;
+//                straggler.h, shared with the dist and resident engines),
 //                implemented as host-side due-times on the dispatch queue —
 //                no thread sleeps, no locks, no GIL (released for the whole
 //                run).
@@ -77,8 +78,12 @@
 
 #include <hip/hip_runtime.h>
 
+#define HIP_CHECK_WHO "native engine"
 #include "grad_wave.h"
+#include "host_util.h"
+#include "launchers.h"
 #include "multi_update.h"
+#include "straggler.h"
 
 #include <algorithm>
 #include <chrono>
@@ -86,6 +91,7 @@
 #include <cstdint>
 #include <deque>
 #include <limits>
+#include <numeric>
 #include <stdexcept>
 #include <string>
 #include <thread>
@@ -93,89 +99,7 @@
 
 namespace py = pybind11;
 
-extern "C" {
-int query_grad_grid(long);
-void launch_grad_csr_wave(const void*, const void*, uint64_t, double, int,
-                          int, int, hipStream_t);
-void launch_saga_commit_wave(const void*, const void*, hipStream_t);
-void launch_scan_rows_wave(const void*, const void*, uint64_t, double,
-                           hipStream_t);
-void launch_alpha_gather_wave(const void*, const void*, hipStream_t);
-void launch_grad_dense_wave(const void*, const void*, long, int, uint64_t,
-                            double, int, int, int, hipStream_t);
-void launch_grad_dense_flag(const void*, const float*, const float*,
-                            float*, float*, int*, const int*, long, int,
-                            uint64_t, uint32_t, uint64_t, double, int, int,
-                            hipStream_t, unsigned long long*,
-                            unsigned long long, unsigned long long*);
-void launch_saga_grad_dense_flag(const void*, const float*, const float*,
-                                 float*, float*, float*, int*, int*, float*,
-                                 int*, const int*, int, long, int, uint64_t,
-                                 uint32_t, uint64_t, double, int, int,
-                                 hipStream_t, unsigned long long*,
-                                 unsigned long long, unsigned long long*);
-void launch_grad_csr_flag(const int*, const int*, const void*, const float*,
-                          const float*, float*, int*, const int*, long,
-                          uint64_t, uint32_t, uint64_t, double, int, int,
-                          hipStream_t, unsigned long long*,
-                          unsigned long long, unsigned long long*);
-void launch_saga_grad_csr_flag(const int*, const int*, const void*,
-                               const float*, const float*, float*, float*,
-                               int*, int*, float*, int*, const int*, int,
-                               long, uint64_t, uint32_t, uint64_t, double,
-                               int, int, hipStream_t, unsigned long long*,
-                               unsigned long long, unsigned long long*);
-void launch_multi_update(float*, float* const*, float* const*, float*, float,
-                         float, float, int, const MultiUpdateArgs*, int,
-                         float, float, hipStream_t);
-void launch_saga_commit_devn(float*, const int*, const float*, const int*,
-                             int, hipStream_t);
-void launch_scan_rows(const float*, int*, float*, int*, const int*, long,
-                      uint64_t, uint32_t, uint64_t, double, hipStream_t);
-void launch_alpha_gather(float*, const float*, const int*, const int*, int,
-                         hipStream_t);
-void launch_sync_round_update(float*, float* const*, int* const*, float*,
-                              float*, int*, int, int, int, float, float,
-                              float, float, int, float, float, float,
-                              hipStream_t);
-}
-
 namespace {
-
-#define HIP_CHECK(x)                                                       \
-  do {                                                                     \
-    hipError_t _e = (x);                                                   \
-    if (_e != hipSuccess)                                                  \
-      throw std::runtime_error(std::string("native engine: ") +            \
-                               hipGetErrorString(_e) + " @ " #x);          \
-  } while (0)
-
-// Host Philox (must match csrc/philox.h / utils/philox.py) for the
-// reproducible straggler draws (uniform01 counters (i,0,round,stream)).
-inline uint32_t philox_host_x0(uint64_t seed, uint32_t c0, uint32_t c1,
-                               uint32_t c2, uint32_t c3) {
-  uint32_t k0 = (uint32_t)(seed & 0xFFFFFFFFull);
-  uint32_t k1 = (uint32_t)(seed >> 32);
-  for (int r = 0; r < 10; ++r) {
-    uint64_t p0 = 0xD2511F53ull * (uint64_t)c0;
-    uint64_t p1 = 0xCD9E8D57ull * (uint64_t)c2;
-    uint32_t hi0 = (uint32_t)(p0 >> 32), lo0 = (uint32_t)p0;
-    uint32_t hi1 = (uint32_t)(p1 >> 32), lo1 = (uint32_t)p1;
-    uint32_t n0 = hi1 ^ c1 ^ k0;
-    uint32_t n1 = lo1;
-    uint32_t n2 = hi0 ^ c3 ^ k1;
-    uint32_t n3 = lo0;
-    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  return c0;
-}
-
-inline double uniform01_host(uint64_t seed, uint32_t round_k,
-                             uint32_t stream) {
-  return philox_host_x0(seed, 0u, 0u, round_k, stream) / 4294967296.0;
-}
 
 struct WorkerBuf {
   // device pointers supplied by Python (torch tensors kept alive there)
@@ -237,9 +161,20 @@ struct EngineCfg {
   long ckpt_every = 0;  // checkpoint when k crosses a multiple (0 = off)
 };
 
-double now_s() {
-  using clk = std::chrono::steady_clock;
-  return std::chrono::duration<double>(clk::now().time_since_epoch()).count();
+// A host vector as a device table, and its release (null-safe, nulls p).
+template <class T>
+T* upload_table(const std::vector<T>& h) {
+  T* dev = nullptr;
+  HIP_CHECK(hipMalloc((void**)&dev, sizeof(T) * h.size()));
+  HIP_CHECK(hipMemcpy(dev, h.data(), sizeof(T) * h.size(),
+                      hipMemcpyHostToDevice));
+  return dev;
+}
+
+template <class T>
+void free_table(T*& p) {
+  if (p) HIP_CHECK(hipFree(p));
+  p = nullptr;
 }
 
 struct NativeEngine {
@@ -255,13 +190,9 @@ struct NativeEngine {
   std::deque<std::pair<double, int>> delayed;  // (due time, worker)
   long applied = 0, rejected = 0;
   long max_staleness_seen = -1;
-  // delay calibration (reference :177-186,:247-252)
-  double cul_time_ms = 0;
-  long cul_count = 0;
-  double avg_delay_ms = 0;
-  bool delay_flag = false;
-  // straggler sets (reference :124-141)
-  std::vector<int> straggler_kind;  // 0 none, 1 normal, 2 longtail
+  // delay calibration (reference :177-186,:247-252); the straggler model
+  // itself is straggler.h
+  straggler::Calibration cal;
   double mark_lo_t = 0, mark_hi_t = 0;
   std::vector<double> snap_ms;  // host stamps for the optVars snapshots
   double run_t0 = 0;
@@ -291,6 +222,7 @@ struct NativeEngine {
   int** ctr_tab_dev = nullptr;
   int* sync_ticket_dev = nullptr;
   bool sync_staged = false;  // the last sync SAGA round's history is staged
+  std::vector<int> all_wids;  // 0..P-1: a sync round spans every worker
   // periodic checkpoint: append_accepted / the sync loop compare k against
   // next_ckpt (LONG_MAX when off — the only cost of the feature being off)
   py::object ckpt_cb;  // Python callable({k, clock, delay_state}); GIL-guarded
@@ -308,32 +240,9 @@ struct NativeEngine {
       next_ckpt = (k / cfg.ckpt_every + 1) * cfg.ckpt_every;
   }
 
-  void init_stragglers() {
-    straggler_kind.assign(cfg.P, 0);
-    const int length = (int)std::lround(0.25 * cfg.P);
-    const int length_normal = (int)std::lround(0.8 * length);
-    const int length_longtail = length - length_normal;
-    for (int c = 0; c < length; ++c) {
-      const int idx = c * 4;
-      if (idx < cfg.P) straggler_kind[idx] = (c < length_longtail) ? 2 : 1;
-    }
-  }
-
   double delay_ms_for(int wid, long round_k) const {
-    if (!delay_flag || cfg.coeff == 0.0) return 0.0;
-    if (cfg.coeff != -1.0) {
-      if (wid == 0 && cfg.coeff > 0) return std::round(cfg.coeff * avg_delay_ms);
-      return 0.0;
-    }
-    if (straggler_kind[wid] == 2) {
-      const double u = uniform01_host(cfg.seed, (uint32_t)round_k, wid);
-      return std::round((u * 7.5 + 2.5) * avg_delay_ms);
-    }
-    if (straggler_kind[wid] == 1) {
-      const double u = uniform01_host(cfg.seed, (uint32_t)round_k, wid);
-      return std::round((u + 1.5) * avg_delay_ms);
-    }
-    return 0.0;
+    return straggler::delay_ms(cfg.P, cfg.coeff, cfg.seed, cal.avg_delay_ms,
+                               cal.delay_flag, wid, round_k);
   }
 
   int gate() const {
@@ -415,6 +324,58 @@ struct NativeEngine {
     HIP_CHECK(hipGetLastError());
   }
 
+  // Commit the staged SAGA history of workers wids[0..n) on ``stream`` (the
+  // count is read on-device — no D2H sync). With the commit slot table (wave
+  // mode) that is ONE commit + staging-reset kernel: the gradient ran on a
+  // wave stream, so the staging must be read with the RMW-load commit kernel
+  // (normal loads could hit a stale L2 line across the stream boundary).
+  // Otherwise one launch per worker; spill mode scatters straight into the
+  // pinned master table. The caller clears its own pending mark.
+  void commit_history(const int* wids, int n, hipStream_t stream) {
+    if (commit_slots_dev) {
+      CsrCommitCmd cc;
+      cc.n = n;
+      cc.bper = 16;
+      for (int i = 0; i < n; ++i) {
+        cc.wid[i] = wids[i];
+        cc.do_commit[i] = 1;
+      }
+      if (n > 0) {
+        launch_saga_commit_wave(commit_slots_dev, &cc, stream);
+        HIP_CHECK(hipGetLastError());
+      }
+      return;
+    }
+    for (int i = 0; i < n; ++i) {
+      WorkerBuf& wk = ws[wids[i]];
+      float* dst = (float*)(wk.alpha_host ? wk.alpha_host : wk.alpha);
+      launch_saga_commit_devn(dst, (const int*)wk.idx_out,
+                              (const float*)wk.e_out,
+                              (const int*)(wk.ctr + 4), wk.saga_cap, stream);
+      HIP_CHECK(hipGetLastError());
+    }
+  }
+
+  // Dispatch bookkeeping of the per-worker and the wave path: the submit
+  // stamps, then the serial the grad kernel's last block will publish.
+  void book_submit(WorkerBuf& wk, double t_now) {
+    if (wk.finish_t == 0) wk.finish_t = t_now;  // first dispatch: no wait
+    wk.waiting_ms += (t_now - wk.finish_t) * 1000.0;
+    wk.submit_t = t_now;
+    wk.busy = true;
+    wk.ts = clock;
+    wk.k_submit = k;
+  }
+
+  void book_in_flight(WorkerBuf& wk, int wid) {
+    if (wk.in_flight)
+      throw std::runtime_error(
+          "native engine invariant: dispatch while a round is in flight "
+          "(worker " + std::to_string(wid) + ")");
+    wk.round_serial += 1;
+    wk.in_flight = true;
+  }
+
   // Common dispatch tail: SAGA commit of the previous accepted round (count
   // read on-device — no D2H sync), waiting-time bookkeeping, grad launch
   // ordered after the latest applied update, completion event.
@@ -424,34 +385,10 @@ struct NativeEngine {
   void dispatch_impl(int wid, double t_now, bool copy_w) {
     WorkerBuf& wk = ws[wid];
     // accept-gated SAGA history commit from the worker's previous round
-    // (spill mode: scatter straight into the pinned master table)
-    if (cfg.algo == 1 && wk.pending_commit) {
-      if (commit_slots_dev) {
-        // wave mode: the previous grad ran on a wave stream, so the
-        // staging must be read with the RMW-load commit kernel (normal
-        // loads could hit a stale L2 line across the stream boundary)
-        CsrCommitCmd cc;
-        cc.n = 1;
-        cc.bper = 16;
-        cc.wid[0] = wid;
-        cc.do_commit[0] = 1;
-        launch_saga_commit_wave(commit_slots_dev, &cc, wk.stream);
-      } else {
-        float* dst = (float*)(wk.alpha_host ? wk.alpha_host : wk.alpha);
-        launch_saga_commit_devn(dst, (const int*)wk.idx_out,
-                                (const float*)wk.e_out,
-                                (const int*)(wk.ctr + 4), wk.saga_cap,
-                                wk.stream);
-      }
-      HIP_CHECK(hipGetLastError());
-    }
+    if (cfg.algo == 1 && wk.pending_commit)
+      commit_history(&wid, 1, wk.stream);
     wk.pending_commit = false;
-    if (wk.finish_t == 0) wk.finish_t = t_now;  // first dispatch: no wait
-    wk.waiting_ms += (t_now - wk.finish_t) * 1000.0;
-    wk.submit_t = t_now;
-    wk.busy = true;
-    wk.ts = clock;
-    wk.k_submit = k;
+    book_submit(wk, t_now);
     // versioned weights: the worker computes against the w it was
     // dispatched with (ASYNCbroadcast semantics) — ordered after the
     // latest applied update either way
@@ -460,12 +397,7 @@ struct NativeEngine {
       HIP_CHECK(hipMemcpyAsync((void*)wk.wbuf, (const void*)w,
                                (size_t)cfg.d * 4, hipMemcpyDeviceToDevice,
                                wk.stream));
-    if (wk.in_flight)
-      throw std::runtime_error(
-          "native engine invariant: dispatch while a round is in flight "
-          "(worker " + std::to_string(wid) + ")");
-    wk.round_serial += 1;  // the grad kernel's last block publishes this
-    wk.in_flight = true;
+    book_in_flight(wk, wid);
     launch_grad(wk, wk.k_submit + 1);  // reference seed+k+1
     // no hipEventRecord: completion = *done_flag == round_serial (plain
     // pinned-memory read, ~0 host cost vs ~1-2 us per hipEventQuery)
@@ -478,23 +410,13 @@ struct NativeEngine {
   // ASGD-only: no SAGA commit to chain.
   void dispatch_book(int wid, double t_now) {
     WorkerBuf& wk = ws[wid];
-    if (wk.finish_t == 0) wk.finish_t = t_now;  // first dispatch: no wait
-    wk.waiting_ms += (t_now - wk.finish_t) * 1000.0;
-    wk.submit_t = t_now;
-    wk.busy = true;
-    wk.ts = clock;
-    wk.k_submit = k;
+    book_submit(wk, t_now);
     if (wk.g_dirty) {  // rejected round left sums; zero on the wave stream
       HIP_CHECK(hipMemsetAsync((void*)wk.g, 0, (size_t)cfg.d * 4,
                                cur_wst));
       wk.g_dirty = false;
     }
-    if (wk.in_flight)
-      throw std::runtime_error(
-          "native engine invariant: dispatch while a round is in flight "
-          "(worker " + std::to_string(wid) + ")");
-    wk.round_serial += 1;
-    wk.in_flight = true;
+    book_in_flight(wk, wid);
   }
 
   void dispatch_wave(const std::vector<int>& ready, double t_now) {
@@ -518,39 +440,43 @@ struct NativeEngine {
         HIP_CHECK(hipGetLastError());
       }
     }
+    for (int wid : ready) dispatch_book(wid, t_now);
+    launch_grad_wave(ready.data(), (int)ready.size(), cur_wst);
+  }
+
+  // One gradient wave over workers wids[0..n) on ``stream``, each at the
+  // round key (k_submit + 1, reference seed+k+1) and completion serial its
+  // WorkerBuf holds: the dense or the CSR wave kernel, by which slot table
+  // setup_tables built.
+  void launch_grad_wave(const int* wids, int n, hipStream_t stream) {
+    if (n <= 0) return;
     GradWaveCmd cmd;
-    cmd.n = 0;
+    cmd.n = n;
     cmd.bper = wave_bper;
     cmd.interleave = wave_interleave;
-    for (int wid : ready) {
-      dispatch_book(wid, t_now);
-      WorkerBuf& wk = ws[wid];
-      cmd.wid[cmd.n] = wid;
-      cmd.round_k[cmd.n] = (unsigned int)(wk.k_submit + 1);
-      cmd.done_val[cmd.n] = wk.round_serial;
-      cmd.n += 1;
+    for (int i = 0; i < n; ++i) {
+      const WorkerBuf& wk = ws[wids[i]];
+      cmd.wid[i] = wids[i];
+      cmd.round_k[i] = (unsigned int)(wk.k_submit + 1);
+      cmd.done_val[i] = wk.round_serial;
     }
-    if (cmd.n > 0) {
-      if (slots_dev) {
-        if (wave_spill) {
-          // spill refresh, stream-ordered: recompute the round's Philox
-          // row sets, then gather those master entries into the staging
-          // tables the gradient reads
-          launch_scan_rows_wave(slots_dev, &cmd, cfg.seed, cfg.rate,
-                                cur_wst);
-          launch_alpha_gather_wave(slots_dev, &cmd, cur_wst);
-        }
-        launch_grad_dense_wave(slots_dev, &cmd, wave_max_rows, cfg.d,
-                               cfg.seed, cfg.rate, cfg.objective,
-                               ws[0].x_is_bf16, cfg.algo == 1 ? 1 : 0,
-                               cur_wst);
-      } else {
-        launch_grad_csr_wave(csr_slots_dev, &cmd, cfg.seed, cfg.rate,
-                             cfg.objective, ws[0].x_is_bf16,
-                             cfg.algo == 1 ? 1 : 0, cur_wst);
+    if (slots_dev) {
+      if (wave_spill) {
+        // spill refresh, stream-ordered: recompute the round's Philox row
+        // sets, then gather those master entries into the staging tables
+        // the gradient reads
+        launch_scan_rows_wave(slots_dev, &cmd, cfg.seed, cfg.rate, stream);
+        launch_alpha_gather_wave(slots_dev, &cmd, stream);
       }
-      HIP_CHECK(hipGetLastError());
+      launch_grad_dense_wave(slots_dev, &cmd, wave_max_rows, cfg.d, cfg.seed,
+                             cfg.rate, cfg.objective, ws[0].x_is_bf16,
+                             cfg.algo == 1 ? 1 : 0, stream);
+    } else {
+      launch_grad_csr_wave(csr_slots_dev, &cmd, cfg.seed, cfg.rate,
+                           cfg.objective, ws[0].x_is_bf16,
+                           cfg.algo == 1 ? 1 : 0, stream);
     }
+    HIP_CHECK(hipGetLastError());
   }
 
   // Pop every pending worker that may dispatch now: stragglers move to the
@@ -560,10 +486,7 @@ struct NativeEngine {
     if (pendingq.empty()) return;
     if (available() < gate()) return;
     // delay calibration activation (reference :247-252)
-    if (!delay_flag && k > cfg.calib_window) {
-      if (cul_count > 0) avg_delay_ms = cul_time_ms / cul_count;
-      delay_flag = true;
-    }
+    cal.maybe_activate(k, cfg.calib_window);
     const size_t qn = pendingq.size();
     for (size_t i = 0; i < qn; ++i) {
       const int wid = pendingq.front();
@@ -599,10 +522,7 @@ struct NativeEngine {
     const bool accept = (cfg.algo == 1) ? (k - wk.ts) <= cfg.taw
                                         : staleness <= cfg.taw;
     if (accept) {
-      if (k < cfg.calib_window) {
-        cul_time_ms += rt * 1000.0;
-        cul_count += 1;
-      }
+      if (k < cfg.calib_window) cal.record(rt * 1000.0, 1);
     } else {
       rejected += 1;
       wk.pending_commit = false;
@@ -708,13 +628,24 @@ struct NativeEngine {
     double checkpoint_ms = 0;
   };
 
-  void fill_result_state(Result& out) const {
+  // Everything run() and run_sync() report alike; rejected, max_staleness
+  // and waits are the caller's.
+  Result make_result(double elapsed_ms) const {
+    Result out;
+    out.k = k;
+    out.elapsed_ms = elapsed_ms;
+    out.applied = applied;
+    out.mark_lo_t = mark_lo_t;
+    out.mark_hi_t = mark_hi_t;
+    out.avg_delay = cal.avg_delay_ms;
+    out.snap_ms = snap_ms;
     out.clock = clock;
-    out.delay_flag = delay_flag;
-    out.cul_time_ms = cul_time_ms;
-    out.cul_count = cul_count;
+    out.delay_flag = cal.delay_flag;
+    out.cul_time_ms = cal.cul_time_ms;
+    out.cul_count = (long)cal.cul_count;
     out.checkpoints = checkpoints;
     out.checkpoint_ms = checkpoint_ms;
+    return out;
   }
 
   // -- quiescent state + checkpoint callback -------------------------------
@@ -727,33 +658,13 @@ struct NativeEngine {
   // Afterwards w, alpha_bar and the history tables describe iterate k.
   void flush_quiescent() {
     if (cfg.algo == 1) {
-      if (commit_slots_dev) {
-        CsrCommitCmd cc;
-        cc.n = 0;
-        cc.bper = 16;
-        for (int i = 0; i < cfg.P; ++i) {
-          if (!ws[i].pending_commit) continue;
-          cc.wid[cc.n] = i;
-          cc.do_commit[cc.n] = 1;
-          cc.n += 1;
+      std::vector<int> pend;
+      for (int i = 0; i < cfg.P; ++i)
+        if (ws[i].pending_commit) {
+          pend.push_back(i);
           ws[i].pending_commit = false;
         }
-        if (cc.n > 0) {
-          launch_saga_commit_wave(commit_slots_dev, &cc, sstream);
-          HIP_CHECK(hipGetLastError());
-        }
-      } else {
-        for (auto& wk : ws) {
-          if (!wk.pending_commit) continue;
-          float* dst = (float*)(wk.alpha_host ? wk.alpha_host : wk.alpha);
-          launch_saga_commit_devn(dst, (const int*)wk.idx_out,
-                                  (const float*)wk.e_out,
-                                  (const int*)(wk.ctr + 4), wk.saga_cap,
-                                  sstream);
-          HIP_CHECK(hipGetLastError());
-          wk.pending_commit = false;
-        }
-      }
+      commit_history(pend.data(), (int)pend.size(), sstream);
     }
     for (auto& wk : ws) {
       if (!wk.g_dirty) continue;
@@ -776,10 +687,10 @@ struct NativeEngine {
     try {
       py::gil_scoped_acquire gil;
       py::dict ds;
-      ds["avg_delay_ms"] = avg_delay_ms;
-      ds["delay_flag"] = delay_flag;
-      ds["cul_time_ms"] = cul_time_ms;
-      ds["cul_count"] = cul_count;
+      ds["avg_delay_ms"] = cal.avg_delay_ms;
+      ds["delay_flag"] = cal.delay_flag;
+      ds["cul_time_ms"] = cal.cul_time_ms;
+      ds["cul_count"] = cal.cul_count;
       py::dict st;
       st["k"] = k;
       st["clock"] = clock;
@@ -867,11 +778,7 @@ struct NativeEngine {
           hs[i].sylist = (float*)ws[i].sylist;
           hs[i].scnt = (int*)ws[i].scnt;
         }
-        HIP_CHECK(hipMalloc((void**)&slots_dev,
-                            sizeof(GradWaveSlot) * cfg.P));
-        HIP_CHECK(hipMemcpy(slots_dev, hs.data(),
-                            sizeof(GradWaveSlot) * cfg.P,
-                            hipMemcpyHostToDevice));
+        slots_dev = upload_table(hs);
       } else {
         std::vector<CsrWaveSlot> hs(cfg.P);
         for (int i = 0; i < cfg.P; ++i) {
@@ -891,11 +798,7 @@ struct NativeEngine {
           hs[i].done_flag = (unsigned long long*)ws[i].done_flag;
           hs[i].done_arr = ws[i].done_arr;
         }
-        HIP_CHECK(hipMalloc((void**)&csr_slots_dev,
-                            sizeof(CsrWaveSlot) * cfg.P));
-        HIP_CHECK(hipMemcpy(csr_slots_dev, hs.data(),
-                            sizeof(CsrWaveSlot) * cfg.P,
-                            hipMemcpyHostToDevice));
+        csr_slots_dev = upload_table(hs);
       }
       if (cfg.algo == 1) {  // unified commit view (dense + CSR SAGA)
         std::vector<CommitSlot> cs(cfg.P);
@@ -909,11 +812,7 @@ struct NativeEngine {
           cs[i].n_out = (int*)ws[i].ctr;
           cs[i].arr = ws[i].done_arr;
         }
-        HIP_CHECK(hipMalloc((void**)&commit_slots_dev,
-                            sizeof(CommitSlot) * cfg.P));
-        HIP_CHECK(hipMemcpy(commit_slots_dev, cs.data(),
-                            sizeof(CommitSlot) * cfg.P,
-                            hipMemcpyHostToDevice));
+        commit_slots_dev = upload_table(cs);
       }
       if (!sync)
         for (int i = 0; i < NWSTREAM; ++i)
@@ -947,23 +846,16 @@ struct NativeEngine {
         hw[i] = (float*)ws[i].wbuf;
         mu_vec4 = mu_vec4 && ((ws[i].g | ws[i].wbuf) & 15) == 0;
       }
-      HIP_CHECK(hipMalloc(&g_tab_dev, cfg.P * sizeof(float*)));
-      HIP_CHECK(hipMalloc(&wbuf_tab_dev, cfg.P * sizeof(float*)));
-      HIP_CHECK(hipMemcpy(g_tab_dev, hg.data(), cfg.P * sizeof(float*),
-                          hipMemcpyHostToDevice));
-      HIP_CHECK(hipMemcpy(wbuf_tab_dev, hw.data(), cfg.P * sizeof(float*),
-                          hipMemcpyHostToDevice));
+      g_tab_dev = upload_table(hg);
+      wbuf_tab_dev = upload_table(hw);
     }
     if (sync) {  // sample-counter table + reset ticket (sync_round_update)
       std::vector<int*> hc(cfg.P);
       for (int i = 0; i < cfg.P; ++i) hc[i] = (int*)ws[i].ctr;
-      HIP_CHECK(hipMalloc(&ctr_tab_dev, cfg.P * sizeof(int*)));
-      HIP_CHECK(hipMemcpy(ctr_tab_dev, hc.data(), cfg.P * sizeof(int*),
-                          hipMemcpyHostToDevice));
+      ctr_tab_dev = upload_table(hc);
       HIP_CHECK(hipMalloc(&sync_ticket_dev, 16));
       HIP_CHECK(hipMemset(sync_ticket_dev, 0, 16));
     }
-    init_stragglers();
   }
 
   // Frees everything setup_tables made. The caller has drained every
@@ -980,20 +872,10 @@ struct NativeEngine {
       HIP_CHECK(hipHostFree((void*)flags_host));
       flags_host = nullptr;
     }
-    HIP_CHECK(hipFree(arr_dev));
-    arr_dev = nullptr;
-    if (slots_dev) {
-      HIP_CHECK(hipFree(slots_dev));
-      slots_dev = nullptr;
-    }
-    if (csr_slots_dev) {
-      HIP_CHECK(hipFree(csr_slots_dev));
-      csr_slots_dev = nullptr;
-    }
-    if (commit_slots_dev) {
-      HIP_CHECK(hipFree(commit_slots_dev));
-      commit_slots_dev = nullptr;
-    }
+    free_table(arr_dev);
+    free_table(slots_dev);
+    free_table(csr_slots_dev);
+    free_table(commit_slots_dev);
     for (int i = 0; i < NWSTREAM; ++i)
       if (wstreams[i]) {
         HIP_CHECK(hipStreamDestroy(wstreams[i]));
@@ -1001,17 +883,10 @@ struct NativeEngine {
       }
     HIP_CHECK(hipEventDestroy(update_ev));
     HIP_CHECK(hipStreamDestroy(sstream));
-    HIP_CHECK(hipFree(g_tab_dev));
-    HIP_CHECK(hipFree(wbuf_tab_dev));
-    g_tab_dev = wbuf_tab_dev = nullptr;
-    if (ctr_tab_dev) {
-      HIP_CHECK(hipFree(ctr_tab_dev));
-      ctr_tab_dev = nullptr;
-    }
-    if (sync_ticket_dev) {
-      HIP_CHECK(hipFree(sync_ticket_dev));
-      sync_ticket_dev = nullptr;
-    }
+    free_table(g_tab_dev);
+    free_table(wbuf_tab_dev);
+    free_table(ctr_tab_dev);
+    free_table(sync_ticket_dev);
   }
 
   // One sweep over the workers' completion lines: book every finished
@@ -1165,30 +1040,16 @@ struct NativeEngine {
       }
     flush_quiescent();
     if (ckpt_due) call_checkpoint();  // k crossed a multiple as the run ended
-    Result out;
-    out.k = k;
-    out.elapsed_ms = (t1 - t0) * 1000.0;
-    out.applied = applied;
+    Result out = make_result((t1 - t0) * 1000.0);
     out.rejected = rejected;
     out.max_staleness = max_staleness_seen;
-    out.mark_lo_t = mark_lo_t;
-    out.mark_hi_t = mark_hi_t;
-    out.avg_delay = avg_delay_ms;
-    out.snap_ms = snap_ms;
     for (auto& wk : ws) out.waits.push_back(wk.waiting_ms);
-    fill_result_state(out);
     teardown_tables();
     return out;
   }
 
   // -- synchronous mode (see the file header) ------------------------------
 
-  // Round kr's gradient work, all on the server stream: (SAGA) the commit
-  // of the previous round's staged history, unless a checkpoint already
-  // committed it — every sync round is accepted — then one gradient wave
-  // over ALL P slots against w itself. Shapes the
-  // wave kernels do not cover take the per-worker launch_grad on that same
-  // stream (setup_tables(true) pointed wk.stream at sstream, wk.wbuf at w).
   // Commit the previous sync SAGA round's staged history for all P workers
   // on the server stream (no-op when nothing is staged). The wave kernel
   // also resets the staging counters; the per-worker form leaves that to
@@ -1196,54 +1057,27 @@ struct NativeEngine {
   // after a checkpoint from committing the same staging again.
   void sync_commit_staged() {
     if (cfg.algo != 1 || !sync_staged) return;
-    if (commit_slots_dev) {
-      CsrCommitCmd cc{};
-      cc.n = cfg.P;
-      cc.bper = 16;
-      for (int i = 0; i < cfg.P; ++i) {
-        cc.wid[i] = i;
-        cc.do_commit[i] = 1;
-      }
-      launch_saga_commit_wave(commit_slots_dev, &cc, sstream);
-      HIP_CHECK(hipGetLastError());
-    } else {
-      for (auto& wk : ws) {
-        launch_saga_commit_devn((float*)wk.alpha, (const int*)wk.idx_out,
-                                (const float*)wk.e_out,
-                                (const int*)(wk.ctr + 4), wk.saga_cap,
-                                sstream);
-        HIP_CHECK(hipGetLastError());
-      }
-    }
+    commit_history(all_wids.data(), cfg.P, sstream);
     sync_staged = false;
   }
 
+  // Round kr's gradient work, all on the server stream: (SAGA) the commit
+  // of the previous round's staged history, unless a checkpoint already
+  // committed it — every sync round is accepted — then one gradient wave
+  // over ALL P slots against w itself. Shapes the wave kernels do not
+  // cover take the per-worker launch_grad on that same stream
+  // (setup_tables(true) pointed wk.stream at sstream, wk.wbuf at w).
   void sync_enqueue_grad(long kr) {
-    const long round_key = kr + 1;  // reference seed+k+1
     sync_commit_staged();
     if (!wave_ok) {
       // SAGA: launch_grad re-zeroes ctr after the commit
-      for (auto& wk : ws) launch_grad(wk, round_key);
+      for (auto& wk : ws) launch_grad(wk, kr + 1);  // reference seed+k+1
       return;
     }
-    GradWaveCmd cmd{};
-    cmd.n = cfg.P;
-    cmd.bper = wave_bper;
-    cmd.interleave = wave_interleave;
-    for (int i = 0; i < cfg.P; ++i) {
-      cmd.wid[i] = i;
-      cmd.round_k[i] = (unsigned int)round_key;
-      cmd.done_val[i] = 0;  // unused: the sync slots carry a null done_flag
-    }
-    if (slots_dev)
-      launch_grad_dense_wave(slots_dev, &cmd, wave_max_rows, cfg.d, cfg.seed,
-                             cfg.rate, cfg.objective, ws[0].x_is_bf16,
-                             cfg.algo == 1 ? 1 : 0, sstream);
-    else
-      launch_grad_csr_wave(csr_slots_dev, &cmd, cfg.seed, cfg.rate,
-                           cfg.objective, ws[0].x_is_bf16,
-                           cfg.algo == 1 ? 1 : 0, sstream);
-    HIP_CHECK(hipGetLastError());
+    // every slot at round kr; round_serial stays 0 and is unused (the sync
+    // slots carry a null done_flag)
+    for (auto& wk : ws) wk.k_submit = kr;
+    launch_grad_wave(all_wids.data(), cfg.P, sstream);
   }
 
   // The barrier: poll the event recorded behind round kr's update. Bounded
@@ -1279,6 +1113,8 @@ struct NativeEngine {
   Result run_sync(int mode) {
     setup_tables(true);
     arm_start();
+    all_wids.resize(cfg.P);
+    std::iota(all_wids.begin(), all_wids.end(), 0);
     bool vec4 = cfg.d % 4 == 0 &&
                 ((w | alpha_bar | cfg.snap_ring) & 15) == 0;
     for (auto& wk : ws) vec4 = vec4 && (wk.g & 15) == 0;
@@ -1298,11 +1134,7 @@ struct NativeEngine {
     while (k < cfg.iters) {
       const double t_submit = now_s();
       if (t_submit - t0 > cfg.max_wall_s) break;
-      // delay calibration activation (DelayInjector.maybe_activate)
-      if (!delay_flag && k > cfg.calib_window) {
-        if (cul_count > 0) avg_delay_ms = cul_time_ms / cul_count;
-        delay_flag = true;
-      }
+      cal.maybe_activate(k, cfg.calib_window);
       sync_enqueue_grad(k);
       // straggler model: the barrier releases at max(gradient done,
       // t_submit + slowest worker's injected delay). The gradient runs on
@@ -1343,10 +1175,8 @@ struct NativeEngine {
       // every stamp that describes round k is taken here, after the GPU
       // has finished it
       t1 = now_s();
-      if (k * cfg.P < cfg.calib_window) {  // DelayInjector.record_task
-        cul_time_ms += (t1 - t_submit) * 1000.0 * cfg.P;
-        cul_count += cfg.P;
-      }
+      if (k * cfg.P < cfg.calib_window)  // DelayInjector.record_task, P tasks
+        cal.record((t1 - t_submit) * 1000.0 * cfg.P, cfg.P);
       if (snap_now) snap_ms.push_back((t1 - t0) * 1000.0);
       sync_staged = mode == 1;
       k += 1;
@@ -1362,18 +1192,10 @@ struct NativeEngine {
     // quiescent end (after the last t1 stamp): the last round's staged
     // history is committed, so the tables describe iterate k
     sync_quiesce(k - 1);
-    Result out;
-    out.k = k;
-    out.elapsed_ms = (t1 - t0) * 1000.0;
-    out.applied = applied;
+    Result out = make_result((t1 - t0) * 1000.0);
     out.rejected = 0;
     out.max_staleness = 0;
-    out.mark_lo_t = mark_lo_t;
-    out.mark_hi_t = mark_hi_t;
-    out.avg_delay = avg_delay_ms;
-    out.snap_ms = snap_ms;
     out.waits.assign(cfg.P, 0.0);
-    fill_result_state(out);
     teardown_tables();
     return out;
   }
@@ -1422,10 +1244,10 @@ void fill_engine(NativeEngine& eng, py::dict c, py::list workers,
   if (c.contains("delay_state")) {
     // a resumed straggler run neither recalibrates nor runs undelayed
     py::dict ds = py::cast<py::dict>(c["delay_state"]);
-    eng.avg_delay_ms = py::cast<double>(ds["avg_delay_ms"]);
-    eng.delay_flag = py::cast<bool>(ds["delay_flag"]);
-    eng.cul_time_ms = py::cast<double>(ds["cul_time_ms"]);
-    eng.cul_count = py::cast<long>(ds["cul_count"]);
+    eng.cal.avg_delay_ms = py::cast<double>(ds["avg_delay_ms"]);
+    eng.cal.delay_flag = py::cast<bool>(ds["delay_flag"]);
+    eng.cal.cul_time_ms = py::cast<double>(ds["cul_time_ms"]);
+    eng.cal.cul_count = py::cast<long>(ds["cul_count"]);
   }
   if (cfg.ckpt_every > 0 && ckpt_cb.is_none())
     throw std::runtime_error(

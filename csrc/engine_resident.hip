@@ -42,6 +42,7 @@
 
 #include "link.h"
 #include "philox.h"
+#include "straggler.h"
 
 #define RES_BLOCK 256
 #define RES_MAXP 64
@@ -353,7 +354,6 @@ struct ServerState {
   long long ksub[RES_MAXP];
   unsigned long long submit_c[RES_MAXP], finish_c[RES_MAXP];
   unsigned long long due_c[RES_MAXP];  // straggler release time (0 = none)
-  int straggler_kind[RES_MAXP];
   // persistent pending queue (a gate hold must NOT drop requeued workers;
   // ring, thread-0 mutated only)
   int pendq[RES_MAXP];
@@ -387,47 +387,6 @@ struct ServerState {
   int delay_flag;
 };
 
-__device__ __forceinline__ double dev_uniform01(unsigned long long seed,
-                                                unsigned int round_k,
-                                                unsigned int stream) {
-  // counters (0, 0, round, stream) == host uniform01 in the host engines
-  uint32_t c0 = 0, c1 = 0, c2 = round_k, c3 = stream;
-  uint32_t k0 = (uint32_t)(seed & 0xFFFFFFFFull);
-  uint32_t k1 = (uint32_t)(seed >> 32);
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    uint64_t p0 = 0xD2511F53ull * (uint64_t)c0;
-    uint64_t p1 = 0xCD9E8D57ull * (uint64_t)c2;
-    uint32_t hi0 = (uint32_t)(p0 >> 32), lo0 = (uint32_t)p0;
-    uint32_t hi1 = (uint32_t)(p1 >> 32), lo1 = (uint32_t)p1;
-    c0 = hi1 ^ c1 ^ k0;
-    c1 = lo1;
-    c2 = hi0 ^ c3 ^ k1;
-    c3 = lo0;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  return c0 / 4294967296.0;
-}
-
-__device__ double delay_ms_for_dev(const ResidentArgs& a,
-                                   const ServerState& st, int wid,
-                                   long long round_k) {
-  if (!st.delay_flag || a.coeff == 0.0) return 0.0;
-  if (a.coeff != -1.0) {
-    if (wid == 0 && a.coeff > 0)
-      return round(a.coeff * st.avg_delay_ms);
-    return 0.0;
-  }
-  if (st.straggler_kind[wid] == 2)
-    return round((dev_uniform01(a.seed, (unsigned)round_k, wid) * 7.5 + 2.5) *
-                 st.avg_delay_ms);
-  if (st.straggler_kind[wid] == 1)
-    return round((dev_uniform01(a.seed, (unsigned)round_k, wid) + 1.5) *
-                 st.avg_delay_ms);
-  return 0.0;
-}
-
 __device__ void server_block(const ResidentArgs& a) {
   __shared__ ServerState st;
   const int tid = threadIdx.x;
@@ -452,16 +411,6 @@ __device__ void server_block(const ResidentArgs& a) {
       st.ksub[i] = 0;
       st.submit_c[i] = st.finish_c[i] = 0;
       st.due_c[i] = 0;
-      st.straggler_kind[i] = 0;
-    }
-    // reference straggler sets (SparkASGDThread.scala:124-141)
-    const int length = (int)llround(0.25 * a.P);
-    const int length_normal = (int)llround(0.8 * length);
-    const int length_longtail = length - length_normal;
-    for (int c = 0; c < length; ++c) {
-      const int idx = c * 4;
-      if (idx < a.P)
-        st.straggler_kind[idx] = (c < length_longtail) ? 2 : 1;
     }
     a.out[OUT_T0_C] = realtime();
   }
@@ -697,7 +646,9 @@ __device__ void server_block(const ResidentArgs& a) {
         const int w = st.pendq[st.pq_head];
         st.pq_head = (st.pq_head + 1) % RES_MAXP;
         st.pq_n -= 1;
-        const double dly = delay_ms_for_dev(a, st, w, st.k);
+        const double dly =
+            straggler::delay_ms(a.P, a.coeff, a.seed, st.avg_delay_ms,
+                                st.delay_flag != 0, w, st.k);
         if (dly > 0) {
           st.busy[w] = 1;
           st.due_c[w] =
@@ -886,6 +837,19 @@ __global__ void read_realtime_kernel(unsigned long long* out) {
   if (threadIdx.x == 0) *out = __builtin_amdgcn_s_memrealtime();
 }
 
+// Test probe: the straggler model as the server block evaluates it, for n
+// (wid, round_k) pairs. One thread, like the server's control logic.
+__global__ void straggler_probe_kernel(long long P, double coeff,
+                                       unsigned long long seed,
+                                       double avg_ms, const long long* wid,
+                                       const long long* round_k, int n,
+                                       double* out) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  for (int i = 0; i < n; ++i)
+    out[i] = straggler::delay_ms(P, coeff, seed, avg_ms, true, wid[i],
+                                 round_k[i]);
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------- binding
@@ -899,38 +863,28 @@ __global__ void read_realtime_kernel(unsigned long long* out) {
 #include <thread>
 #include <vector>
 
+#define HIP_CHECK_WHO "resident engine"
+#include "host_util.h"
+
 namespace py = pybind11;
 
 namespace {
 
-#define RHIP_CHECK(x)                                                      \
-  do {                                                                     \
-    hipError_t _e = (x);                                                   \
-    if (_e != hipSuccess)                                                  \
-      throw std::runtime_error(std::string("resident engine: ") +          \
-                               hipGetErrorString(_e) + " @ " #x);          \
-  } while (0)
-
-double wall_s() {
-  using clk = std::chrono::steady_clock;
-  return std::chrono::duration<double>(clk::now().time_since_epoch()).count();
-}
-
 // (cycles_at_t0, cycles_per_ms) of the GPU's constant realtime counter
 std::pair<unsigned long long, double> calibrate_realtime(hipStream_t s) {
   unsigned long long* dbuf = nullptr;
-  RHIP_CHECK(hipMalloc(&dbuf, 2 * sizeof(unsigned long long)));
+  HIP_CHECK(hipMalloc(&dbuf, 2 * sizeof(unsigned long long)));
   hipLaunchKernelGGL(read_realtime_kernel, dim3(1), dim3(64), 0, s, dbuf);
-  RHIP_CHECK(hipStreamSynchronize(s));
-  const double w0 = wall_s();
+  HIP_CHECK(hipStreamSynchronize(s));
+  const double w0 = now_s();
   std::this_thread::sleep_for(std::chrono::milliseconds(60));
   hipLaunchKernelGGL(read_realtime_kernel, dim3(1), dim3(64), 0, s,
                      dbuf + 1);
-  RHIP_CHECK(hipStreamSynchronize(s));
-  const double w1 = wall_s();
+  HIP_CHECK(hipStreamSynchronize(s));
+  const double w1 = now_s();
   unsigned long long c[2];
-  RHIP_CHECK(hipMemcpy(c, dbuf, sizeof(c), hipMemcpyDeviceToHost));
-  RHIP_CHECK(hipFree(dbuf));
+  HIP_CHECK(hipMemcpy(c, dbuf, sizeof(c), hipMemcpyDeviceToHost));
+  HIP_CHECK(hipFree(dbuf));
   const double cpm = (double)(c[1] - c[0]) / ((w1 - w0) * 1000.0);
   return {c[1], cpm};
 }
@@ -982,7 +936,7 @@ void register_resident_engine(py::module_& m) {
 
     py::gil_scoped_release rel;
     hipStream_t stream;
-    RHIP_CHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+    HIP_CHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
     auto [c_now, cpm] = calibrate_realtime(stream);
     a.cycles_per_ms = cpm;
     a.deadline_cycles =
@@ -992,15 +946,15 @@ void register_resident_engine(py::module_& m) {
     const size_t lds = (size_t)a.d * sizeof(float);
     int nblk = 0;
     if (a.x_is_bf16)
-      RHIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(
+      HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(
           &nblk, (const void*)resident_engine_kernel<unsigned short>,
           RES_BLOCK, lds));
     else
-      RHIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(
+      HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(
           &nblk, (const void*)resident_engine_kernel<float>, RES_BLOCK,
           lds));
     hipDeviceProp_t prop;
-    RHIP_CHECK(hipGetDeviceProperties(&prop, 0));
+    HIP_CHECK(hipGetDeviceProperties(&prop, 0));
     const int max_resident = nblk * prop.multiProcessorCount;
     if (grid > max_resident)
       throw std::runtime_error(
@@ -1013,14 +967,14 @@ void register_resident_engine(py::module_& m) {
     else
       hipLaunchKernelGGL(resident_engine_kernel<float>, dim3(grid),
                          dim3(RES_BLOCK), lds, stream, a);
-    RHIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipGetLastError());
     // host-side watchdog: poll with a margin past the device deadline
-    const double host_deadline = wall_s() + max_wall_s + 10.0;
+    const double host_deadline = now_s() + max_wall_s + 10.0;
     while (true) {
       const hipError_t q = hipStreamQuery(stream);
       if (q == hipSuccess) break;
-      if (q != hipErrorNotReady) RHIP_CHECK(q);
-      if (wall_s() > host_deadline) {
+      if (q != hipErrorNotReady) HIP_CHECK(q);
+      if (now_s() > host_deadline) {
         (void)hipStreamDestroy(stream);
         throw std::runtime_error(
             "resident engine: kernel exceeded host deadline (device "
@@ -1028,10 +982,10 @@ void register_resident_engine(py::module_& m) {
       }
       std::this_thread::sleep_for(std::chrono::microseconds(200));
     }
-    RHIP_CHECK(hipStreamDestroy(stream));
+    HIP_CHECK(hipStreamDestroy(stream));
 
     unsigned long long out_h[OUT_N];
-    RHIP_CHECK(hipMemcpy(out_h, (const void*)a.out, sizeof(out_h),
+    HIP_CHECK(hipMemcpy(out_h, (const void*)a.out, sizeof(out_h),
                          hipMemcpyDeviceToHost));
     py::gil_scoped_acquire acq;
     py::dict r;
@@ -1071,4 +1025,45 @@ void register_resident_engine(py::module_& m) {
     r["w0_detect_n"] = (long long)out_h[OUT_W0_DET_N];
     return r;
   });
+
+  // The shared straggler model (straggler.h) with calibration active, as
+  // the host engines call it — same arguments as _dist_core's
+  // DistServer.delay_probe — and as the device evaluates it for a list of
+  // (wid, round_k) pairs (one one-thread launch).
+  m.def("straggler_delay_probe",
+        [](long long P, double coeff, uint64_t seed, double avg_ms,
+           long long wid, long long round_k) {
+          return straggler::delay_ms(P, coeff, seed, avg_ms, true, wid,
+                                     round_k);
+        });
+  m.def("straggler_delay_probe_device",
+        [](long long P, double coeff, uint64_t seed, double avg_ms,
+           std::vector<long long> wid, std::vector<long long> round_k) {
+          if (wid.size() != round_k.size())
+            throw std::runtime_error(
+                "straggler_delay_probe_device: len(wid) != len(round_k)");
+          const size_t n = wid.size();
+          std::vector<double> out(n);
+          if (n == 0) return out;
+          char* buf = nullptr;
+          HIP_CHECK(hipMalloc((void**)&buf, 24 * n));
+          long long* wid_d = (long long*)buf;
+          long long* rk_d = wid_d + n;
+          double* out_d = (double*)(rk_d + n);
+          hipError_t e =
+              hipMemcpy(wid_d, wid.data(), 8 * n, hipMemcpyHostToDevice);
+          if (e == hipSuccess)
+            e = hipMemcpy(rk_d, round_k.data(), 8 * n, hipMemcpyHostToDevice);
+          if (e == hipSuccess) {
+            hipLaunchKernelGGL(straggler_probe_kernel, dim3(1), dim3(1), 0,
+                               nullptr, P, coeff, seed, avg_ms, wid_d, rk_d,
+                               (int)n, out_d);
+            e = hipGetLastError();
+          }
+          if (e == hipSuccess)  // the default stream orders this copy
+            e = hipMemcpy(out.data(), out_d, 8 * n, hipMemcpyDeviceToHost);
+          (void)hipFree(buf);
+          HIP_CHECK(e);
+          return out;
+        });
 }

@@ -64,6 +64,7 @@
 #include <type_traits>
 #include "philox.h"
 #include "grad_wave.h"
+#include "launchers.h"  // every extern "C" definition below is checked by it
 #include "link.h"
 #include "update_step.h"
 

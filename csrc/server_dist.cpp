@@ -34,10 +34,7 @@
 #include <torch/extension.h>
 #ifdef __HIP_PLATFORM_AMD__
 #include <c10/hip/HIPStream.h>
-extern "C" void launch_dist_sgd_update(float*, const float*, float, float,
-                                       int, hipStream_t);
-extern "C" void launch_dist_saga_update(float*, const float*, float*, float,
-                                        float, float, int, hipStream_t);
+#include "dist_launchers.h"
 namespace at { namespace cuda {
 using c10::hip::getCurrentHIPStream;
 } }
@@ -55,6 +52,9 @@ using c10::hip::getCurrentHIPStream;
 #include <set>
 #include <thread>
 #include <vector>
+
+#include "host_util.h"
+#include "straggler.h"
 
 namespace {
 
@@ -79,38 +79,6 @@ inline c10::intrusive_ptr<c10d::Work> pg_recv(
     std::vector<at::Tensor>& v, int src, int tag) {
   std::lock_guard<std::mutex> lk(g_pg_mu);
   return pg->recv(v, src, tag);
-}
-
-inline double now_s() {
-  return std::chrono::duration<double>(
-             std::chrono::steady_clock::now().time_since_epoch())
-      .count();
-}
-
-// Host Philox x0 (bit-identical to csrc/philox.h / utils/philox.py) for the
-// reproducible straggler draws: uniform01 counters (0, 0, round, stream).
-inline uint32_t philox_host_x0(uint64_t seed, uint32_t c0, uint32_t c1,
-                               uint32_t c2, uint32_t c3) {
-  uint32_t k0 = (uint32_t)(seed & 0xFFFFFFFFull);
-  uint32_t k1 = (uint32_t)(seed >> 32);
-  for (int r = 0; r < 10; ++r) {
-    uint64_t p0 = 0xD2511F53ull * (uint64_t)c0;
-    uint64_t p1 = 0xCD9E8D57ull * (uint64_t)c2;
-    uint32_t hi0 = (uint32_t)(p0 >> 32), lo0 = (uint32_t)p0;
-    uint32_t hi1 = (uint32_t)(p1 >> 32), lo1 = (uint32_t)p1;
-    c0 = hi1 ^ c1 ^ k0;
-    c1 = lo1;
-    c2 = hi0 ^ c3 ^ k1;
-    c3 = lo0;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  return c0;
-}
-
-inline double uniform01_host(uint64_t seed, uint32_t round_k,
-                             uint32_t stream) {
-  return philox_host_x0(seed, 0u, 0u, round_k, stream) / 4294967296.0;
 }
 
 struct DSCfg {
@@ -173,7 +141,6 @@ class DistServer {
     for (int64_t i = 0; i < cfg_.P; ++i)
       slots_.emplace_back(new Slot());
     for (auto m : mark_at) mark_at_.insert(m);
-    init_stragglers();
   }
 
   // ---- lifecycle ---------------------------------------------------------
@@ -315,39 +282,14 @@ class DistServer {
   std::vector<at::Tensor> opt_w() const { return opt_w_; }
   at::Tensor weights() const { return w_; }
   int64_t max_staleness_seen() const { return max_staleness_; }
-  bool delay_active() const { return delay_flag_; }
-  double avg_delay_ms() const { return avg_delay_ms_; }
+  bool delay_active() const { return cal_.delay_flag; }
+  double avg_delay_ms() const { return cal_.avg_delay_ms; }
 
   // straggler-model probe for cross-checking against engine/delay.py
   static double delay_probe(int64_t P, double coeff, uint64_t seed,
                             double avg_ms, int64_t wid, int64_t round_k) {
-    DSCfg c;
-    c.P = P;
-    c.coeff = coeff;
-    c.seed = seed;
-    DistServer* tmp = nullptr;
-    (void)tmp;
-    // replicate delay_ms_for with an ad-hoc straggler table
-    std::vector<int> kind(P, 0);
-    const int length = (int)std::lround(0.25 * (double)P);
-    const int length_normal = (int)std::lround(0.8 * length);
-    const int length_longtail = length - length_normal;
-    for (int cc = 0; cc < length; ++cc) {
-      const int idx = cc * 4;
-      if (idx < P) kind[idx] = (cc < length_longtail) ? 2 : 1;
-    }
-    if (coeff == 0.0) return 0.0;
-    if (coeff != -1.0)
-      return (wid == 0 && coeff > 0) ? std::round(coeff * avg_ms) : 0.0;
-    if (kind[wid] == 2)
-      return std::round(
-          (uniform01_host(seed, (uint32_t)round_k, (uint32_t)wid) * 7.5 +
-           2.5) * avg_ms);
-    if (kind[wid] == 1)
-      return std::round(
-          (uniform01_host(seed, (uint32_t)round_k, (uint32_t)wid) + 1.5) *
-          avg_ms);
-    return 0.0;
+    return straggler::delay_ms(P, coeff, seed, avg_ms, /*active=*/true, wid,
+                               round_k);
   }
 
  private:
@@ -470,8 +412,7 @@ class DistServer {
       finish_t_[wid] = t_now;
       // delay calibration sample (reference :177-186; Python records wall
       // round time on accepted results only)
-      cul_time_ms_ += (t_now - submit_t_[wid]) * 1000.0;
-      cul_count_ += 1;
+      cal_.record((t_now - submit_t_[wid]) * 1000.0, 1);
       apply(g);
       last_accept_[wid] = 1;
       if (k_ % cfg_.printer_freq == 0 && cfg_.snapshot_weights) {
@@ -558,10 +499,7 @@ class DistServer {
         std::max((int64_t)1, (int64_t)(alive * cfg_.bucket_ratio)));
     const int64_t init_workers = first ? cfg_.P : avail_n;
     if (init_workers < gate) return;
-    if (!delay_flag_ && k_ > cfg_.calib_window) {
-      if (cul_count_ > 0) avg_delay_ms_ = cul_time_ms_ / (double)cul_count_;
-      delay_flag_ = true;
-    }
+    cal_.maybe_activate(k_, cfg_.calib_window);
     at::Tensor w_snap = w_.detach().clone();
     const double t_now = now_s();
     const size_t qn = pending_.size();
@@ -580,7 +518,9 @@ class DistServer {
       m.ts = clock_;
       m.k = k_;
       m.accept = last_accept_[wid] != 0;
-      m.delay_s = delay_ms_for(wid, k_) / 1000.0;
+      m.delay_s = straggler::delay_ms(cfg_.P, cfg_.coeff, cfg_.seed,
+                                      cal_.avg_delay_ms, cal_.delay_flag,
+                                      wid, k_) / 1000.0;
       m.stop = false;
       fill_slot(wid, m);
     }
@@ -602,38 +542,6 @@ class DistServer {
     stop.w = at::Tensor();
     for (int64_t wid = 0; wid < cfg_.P; ++wid) fill_slot((int)wid, stop);
     done_cv_.notify_all();
-  }
-
-  // ---- straggler model (reference SparkASGDThread.scala:124-141,287-312) -
-  void init_stragglers() {
-    straggler_kind_.assign(cfg_.P, 0);
-    const int length = (int)std::lround(0.25 * (double)cfg_.P);
-    const int length_normal = (int)std::lround(0.8 * length);
-    const int length_longtail = length - length_normal;
-    for (int c = 0; c < length; ++c) {
-      const int idx = c * 4;
-      if (idx < cfg_.P) straggler_kind_[idx] = (c < length_longtail) ? 2 : 1;
-    }
-  }
-
-  double delay_ms_for(int wid, int64_t round_k) const {
-    if (!delay_flag_ || cfg_.coeff == 0.0) return 0.0;
-    if (cfg_.coeff != -1.0) {
-      if (wid == 0 && cfg_.coeff > 0)
-        return std::round(cfg_.coeff * avg_delay_ms_);
-      return 0.0;
-    }
-    if (straggler_kind_[wid] == 2) {
-      const double u =
-          uniform01_host(cfg_.seed, (uint32_t)round_k, (uint32_t)wid);
-      return std::round((u * 7.5 + 2.5) * avg_delay_ms_);
-    }
-    if (straggler_kind_[wid] == 1) {
-      const double u =
-          uniform01_host(cfg_.seed, (uint32_t)round_k, (uint32_t)wid);
-      return std::round((u + 1.5) * avg_delay_ms_);
-    }
-    return 0.0;
   }
 
   DSCfg cfg_;
@@ -680,11 +588,7 @@ class DistServer {
   std::vector<int64_t> opt_ms_;
   std::vector<at::Tensor> opt_w_;
   double t0_ = 0;
-  // delay calibration
-  double cul_time_ms_ = 0, avg_delay_ms_ = 0;
-  int64_t cul_count_ = 0;
-  bool delay_flag_ = false;
-  std::vector<int> straggler_kind_;
+  straggler::Calibration cal_;  // delay calibration
 };
 
 }  // namespace
