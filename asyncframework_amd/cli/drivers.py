@@ -6,7 +6,8 @@ Positional args (13) exactly as the reference drivers parse them
 [bucket ratio] [printer freq] [coeff] [seed]; the MLlib baseline takes 8
 (SparkSGDMLLIB.scala:30-37). Extra engine flags (--device, --dtype,
 --objective, --sparse, --history-placement, --test-file / --test-rows /
---threshold for a held-out evaluation) come after the positionals.
+--threshold / --curve-bins for a held-out evaluation) come after the
+positionals.
 
 ``file name`` = 'synthetic' generates data of the given shape instead of
 loading a LibSVM file (no network in this environment).
@@ -85,6 +86,11 @@ def _engine_flags(p: argparse.ArgumentParser) -> None:
                    help="decision threshold of the held-out evaluation "
                         "(default: 0 hinge, 0.5 lsq, probability 0.5 "
                         "logistic)")
+    p.add_argument("--curve-bins", type=int, default=0,
+                   help="with a held-out set: also print the areas under "
+                        "the ROC and PR curves and the best F1 of every "
+                        "logged iterate, from a threshold sweep of this "
+                        "many points (0 = off)")
     p.add_argument("--resume-from", default="",
                    help="restore optimizer state from a checkpoint file "
                         "before running")
@@ -145,7 +151,8 @@ def _evaluate(cfg: EngineConfig, a, res, test_data, sparse: bool,
               device: str) -> None:
     if test_data is not None:
         runner.evaluation_report(cfg, res, test_data, sparse, device=device,
-                                 threshold=a.threshold)
+                                 threshold=a.threshold,
+                                 curve_bins=a.curve_bins)
 
 
 def _run(cfg: EngineConfig, a, app: str, names, vals) -> None:

@@ -306,6 +306,246 @@ def evaluate(X: torch.Tensor, y: torch.Tensor, W: torch.Tensor,
                         n_rows, N_total)
 
 
+class CurveResult(NamedTuple):
+    """Confusion counts of T stacked iterates at K score thresholds each:
+    ``z_thr`` fp64 [T, K], non-decreasing along K; ``tp``/``fp``/``tn``/
+    ``fn`` int64 [T, K] at ``z > z_thr[t, k]``; ``n_pos``/``n_neg`` int64
+    [T]. Every point lies exactly on the iterate's true curve; the
+    thresholds only choose which points.
+
+    The metrics follow MLlib's BinaryClassificationMetrics, in fp64. The
+    by-threshold ones (precision, recall, fpr, f_measure) are [T, K],
+    column k belonging to ``z_thr[:, k]``; roc() and pr() return the curve
+    points in MLlib's order, descending threshold."""
+    z_thr: torch.Tensor
+    tp: torch.Tensor
+    fp: torch.Tensor
+    tn: torch.Tensor
+    fn: torch.Tensor
+    n_pos: torch.Tensor
+    n_neg: torch.Tensor
+
+    @staticmethod
+    def _ratio(num: torch.Tensor, den: torch.Tensor, empty: float
+               ) -> torch.Tensor:
+        """num / den in fp64, `empty` where den == 0."""
+        num, den = torch.broadcast_tensors(num.double(), den.double())
+        safe = torch.where(den == 0, torch.ones_like(den), den)
+        return torch.where(den == 0, torch.full_like(num, empty), num / safe)
+
+    def precision(self) -> torch.Tensor:
+        """tp / (tp + fp); 1 where nothing is predicted positive."""
+        return self._ratio(self.tp, self.tp + self.fp, 1.0)
+
+    def recall(self) -> torch.Tensor:
+        """tp / n_pos (the true-positive rate); 0 without positives."""
+        return self._ratio(self.tp, self.n_pos[:, None], 0.0)
+
+    def fpr(self) -> torch.Tensor:
+        """fp / n_neg; 0 without negatives."""
+        return self._ratio(self.fp, self.n_neg[:, None], 0.0)
+
+    def f_measure(self, beta: float = 1.0) -> torch.Tensor:
+        """(1 + beta^2) p r / (beta^2 p + r); 0 where p + r == 0."""
+        p, r, b2 = self.precision(), self.recall(), float(beta) ** 2
+        return self._ratio((1.0 + b2) * p * r, b2 * p + r, 0.0)
+
+    def roc(self) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(fpr, recall), each [T, K + 2]: the points by descending
+        threshold, with (0, 0) prepended and (1, 1) appended."""
+        T, dev = self.tp.shape[0], self.tp.device
+        zero = torch.zeros(T, 1, dtype=torch.float64, device=dev)
+        one = torch.ones(T, 1, dtype=torch.float64, device=dev)
+        return (torch.cat([zero, self.fpr().flip(1), one], dim=1),
+                torch.cat([zero, self.recall().flip(1), one], dim=1))
+
+    def pr(self) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(recall, precision), each [T, K + 1]: the points by descending
+        threshold, with (0, first precision) prepended (precision 1 when
+        there is no point)."""
+        T, dev = self.tp.shape[0], self.tp.device
+        p = self.precision().flip(1)
+        first = p[:, :1] if p.shape[1] else torch.ones(
+            T, 1, dtype=torch.float64, device=dev)
+        zero = torch.zeros(T, 1, dtype=torch.float64, device=dev)
+        return (torch.cat([zero, self.recall().flip(1)], dim=1),
+                torch.cat([first, p], dim=1))
+
+    @staticmethod
+    def _trapezoid(x: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
+        """AreaUnderCurve: sum of (x1 - x0) (v0 + v1) / 2 over consecutive
+        points."""
+        return ((x[:, 1:] - x[:, :-1]) * (v[:, 1:] + v[:, :-1]) / 2.0).sum(1)
+
+    def auc_roc(self) -> torch.Tensor:
+        """areaUnderROC, fp64 [T]."""
+        return self._trapezoid(*self.roc())
+
+    def auc_pr(self) -> torch.Tensor:
+        """areaUnderPR, fp64 [T]."""
+        return self._trapezoid(*self.pr())
+
+
+_CURVE_SAMPLE_ROWS = 8192
+
+
+def _order_statistics(Z: torch.Tensor, num_bins: int) -> torch.Tensor:
+    """fp64 [T, B]: per column of the sampled scores Z [S, T], the order
+    statistics at the levels (k + 1/2) / B. Non-finite picks are clamped to
+    the fp32 range so that every threshold is finite."""
+    S = Z.shape[0]
+    srt = Z.float().sort(dim=0).values
+    pick = ((torch.arange(num_bins, dtype=torch.float64) + 0.5)
+            * (S / num_bins)).floor().long().clamp(max=S - 1)
+    big = torch.finfo(torch.float32).max
+    thr = srt[pick.to(Z.device)].t().double()
+    return torch.nan_to_num(thr, nan=big, posinf=big, neginf=-big).contiguous()
+
+
+def _sample_rows(n_rows: int, device) -> torch.Tensor:
+    """At most 8192 row ids, floor(i * n / S): strided, no RNG."""
+    S = min(n_rows, _CURVE_SAMPLE_ROWS)
+    return (torch.arange(S, dtype=torch.int64, device=device) * n_rows) // S
+
+
+def _check_bins(num_bins) -> int:
+    if int(num_bins) != num_bins or int(num_bins) < 1:
+        raise ValueError(f"num_bins must be a positive integer, got "
+                         f"{num_bins!r}")
+    return int(num_bins)
+
+
+def curve_thresholds(X: torch.Tensor, W: torch.Tensor, num_bins: int
+                     ) -> torch.Tensor:
+    """Score thresholds for a curve of num_bins points per iterate, fp64
+    [T, num_bins], non-decreasing, without sorting the data: score at most
+    8192 strided rows against all iterates (a small matmul on X's device),
+    sort that sample, and take its order statistics at (k + 1/2) / B.
+    Duplicates are possible; they repeat a point of the curve."""
+    B = _check_bins(num_bins)
+    if X.shape[0] == 0:
+        return torch.zeros(W.shape[0], B, dtype=torch.float64,
+                           device=X.device)
+    rows = _sample_rows(X.shape[0], X.device)
+    Z = X[rows].float() @ W.to(X.device).float().t()
+    return _order_statistics(Z, B)
+
+
+def curve_thresholds_csr(indptr: torch.Tensor, indices: torch.Tensor,
+                         values: torch.Tensor, W: torch.Tensor,
+                         num_bins: int) -> torch.Tensor:
+    """CSR form of curve_thresholds: an index_add_ over the non-zeros of
+    the sampled rows; nothing is densified."""
+    B = _check_bins(num_bins)
+    dev = values.device
+    n_rows = indptr.shape[0] - 1
+    if n_rows <= 0:
+        return torch.zeros(W.shape[0], B, dtype=torch.float64, device=dev)
+    rows = _sample_rows(n_rows, dev)
+    start = indptr[rows].long()
+    count = indptr[rows + 1].long() - start
+    slot = torch.repeat_interleave(
+        torch.arange(rows.numel(), device=dev), count)
+    first = count.cumsum(0) - count  # of each sampled row, in `slot` order
+    p = start[slot] + torch.arange(slot.numel(), device=dev) - first[slot]
+    Wt = W.to(dev).float().t()  # [d, T]
+    Z = torch.zeros(rows.numel(), W.shape[0], dtype=torch.float32, device=dev)
+    Z.index_add_(0, slot, values[p].float()[:, None] * Wt[indices[p].long()])
+    return _order_statistics(Z, B)
+
+
+def _curve_z_thresholds(objective: str, T: int, device, thresholds,
+                        z_thresholds, num_bins, from_bins) -> torch.Tensor:
+    """The fp64 [T, K] score thresholds of an evaluate_curve call."""
+    if objective not in _OBJ_CODE:
+        raise ValueError(f"unknown objective {objective!r}")
+    given = [a is not None for a in (thresholds, z_thresholds, num_bins)]
+    if sum(given) != 1:
+        raise ValueError("give exactly one of thresholds, z_thresholds and "
+                         "num_bins")
+    if num_bins is not None:
+        return from_bins(_check_bins(num_bins))
+    if thresholds is not None:
+        thr = torch.as_tensor(thresholds, dtype=torch.float64).cpu()
+        if thr.dim() != 1:
+            raise ValueError(f"thresholds must be [K], got "
+                             f"{tuple(thr.shape)}")
+        z = torch.tensor([score_threshold(objective, v)
+                          for v in thr.tolist()], dtype=torch.float64)
+        z = z.sort().values
+    else:
+        z = torch.as_tensor(z_thresholds, dtype=torch.float64)
+        if z.dim() not in (1, 2) or (z.dim() == 2 and z.shape[0] != T):
+            raise ValueError(f"z_thresholds must be [K] or [{T}, K], got "
+                             f"{tuple(z.shape)}")
+        if not bool(torch.isfinite(z).all()):
+            raise ValueError("z_thresholds must be finite")
+        if bool((z[..., 1:] < z[..., :-1]).any()):
+            raise ValueError("z_thresholds must be non-decreasing")
+    if z.dim() == 1:
+        z = z[None, :].expand(T, -1)
+    return z.to(device).contiguous()
+
+
+def _curve_zeros(z_thr: torch.Tensor) -> CurveResult:
+    T = z_thr.shape[0]
+    z = lambda *s: torch.zeros(*s, dtype=torch.int64, device=z_thr.device)
+    return CurveResult(z_thr, *(z(*z_thr.shape) for _ in range(4)), z(T),
+                       z(T))
+
+
+def evaluate_curve(X: torch.Tensor, y: torch.Tensor, W: torch.Tensor,
+                   objective: str = "lsq", *, thresholds=None,
+                   z_thresholds=None, num_bins: Optional[int] = None
+                   ) -> CurveResult:
+    """Confusion counts of the stacked iterates W [T, d] on the rows (X, y)
+    at K thresholds per iterate, from one pass over X per tile of iterates
+    and eval_curve_tile() thresholds (the threshold-sweep kernels, K10) —
+    the points of the ROC and PR curves, without a sort. Exactly one of:
+    ``thresholds`` [K] in the user's units (each through score_threshold,
+    then sorted), ``z_thresholds`` [K] or [T, K] finite non-decreasing score
+    thresholds, ``num_bins`` (curve_thresholds picks the thresholds). CPU
+    tensors take the fp64 reference."""
+    if W.dim() != 2 or W.shape[1] != X.shape[1]:
+        raise ValueError(f"W must be [T, {X.shape[1]}], got {tuple(W.shape)}")
+    n_rows, T = X.shape[0], W.shape[0]
+    z_thr = _curve_z_thresholds(
+        objective, T, X.device, thresholds, z_thresholds, num_bins,
+        lambda B: curve_thresholds(X, W, B))
+    if n_rows == 0 or T == 0 or z_thr.shape[1] == 0:
+        return _curve_zeros(z_thr)
+    if X.is_cuda:
+        mod = _require_hip("evaluate_curve")
+        if mod is not None:
+            return CurveResult(z_thr, *mod.evaluate_curve(X, y, W, z_thr))
+    return CurveResult(z_thr, *torch_ref.evaluate_curve(X, y, W, z_thr))
+
+
+def evaluate_curve_csr(indptr: torch.Tensor, indices: torch.Tensor,
+                       values: torch.Tensor, y: torch.Tensor,
+                       W: torch.Tensor, objective: str = "lsq", *,
+                       thresholds=None, z_thresholds=None,
+                       num_bins: Optional[int] = None) -> CurveResult:
+    """CSR form of evaluate_curve."""
+    if W.dim() != 2:
+        raise ValueError(f"W must be [T, d], got {tuple(W.shape)}")
+    n_rows, T = indptr.shape[0] - 1, W.shape[0]
+    z_thr = _curve_z_thresholds(
+        objective, T, values.device, thresholds, z_thresholds, num_bins,
+        lambda B: curve_thresholds_csr(indptr, indices, values, W, B))
+    if n_rows <= 0 or T == 0 or z_thr.shape[1] == 0:
+        return _curve_zeros(z_thr)
+    if values.is_cuda:
+        mod = _require_hip("evaluate_curve_csr")
+        if mod is not None:
+            return CurveResult(
+                z_thr, *mod.evaluate_curve_csr(indptr, indices, values, y, W,
+                                               z_thr))
+    return CurveResult(
+        z_thr, *torch_ref.evaluate_curve_csr(indptr, indices, values, y, W,
+                                             z_thr))
+
+
 def evaluate_csr(indptr: torch.Tensor, indices: torch.Tensor,
                  values: torch.Tensor, y: torch.Tensor, W: torch.Tensor,
                  objective: str = "lsq", *, threshold: Optional[float] = None,

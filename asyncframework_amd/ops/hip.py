@@ -203,6 +203,74 @@ def _eval_buffers(W, d, device, grid, transposed):
     return Wp, n_tiles, part_loss, part_cnt, out_loss, out_cnt
 
 
+def _curve_buffers(W, z_thr, d, device, grid, transposed):
+    """The sweep's buffers: iterate tiles as _eval_buffers, the thresholds
+    z_thr [T, K] padded with +inf to whole tiles and passes, scratch and
+    outputs. Returns (Wtiles, thr, n_tiles, n_pass, part_tot, part_hist,
+    out_cnt, out_tot)."""
+    tt, kt = _hip_core.eval_tile(), _hip_core.eval_curve_tile()
+    T, K = z_thr.shape
+    Wp, n_tiles = _eval_buffers(W, d, device, 0, transposed)[:2]
+    n_pass = (K + kt - 1) // kt
+    thr = torch.full((n_tiles * tt, n_pass * kt), float("inf"),
+                     dtype=torch.float64, device=device)
+    thr[:T, :K] = z_thr.to(device=device, dtype=torch.float64)
+    part_tot = torch.empty(grid * 2 * tt, dtype=torch.int64, device=device)
+    # uint32 counts: a block sees fewer than 2^31 rows
+    part_hist = torch.empty(grid * tt * kt * 2, dtype=torch.int32,
+                            device=device)
+    out_cnt = torch.empty(4, n_tiles * tt, K, dtype=torch.int64,
+                          device=device)
+    out_tot = torch.empty(2, n_tiles * tt, dtype=torch.int64, device=device)
+    return Wp, thr, n_tiles, n_pass, part_tot, part_hist, out_cnt, out_tot
+
+
+def _curve_result(out_cnt, out_tot, T):
+    return (out_cnt[0, :T], out_cnt[1, :T], out_cnt[2, :T], out_cnt[3, :T],
+            out_tot[0, :T], out_tot[1, :T])
+
+
+def evaluate_curve(X, y, W, z_thr):
+    """(tp, fp, tn, fn [T, K], n_pos, n_neg [T]) of the iterates W [T, d]
+    over (X, y) at the score thresholds z_thr [T, K] (rows non-decreasing)."""
+    _chk(X, "X")
+    _chk(y, "y", torch.float32)
+    n_rows, d = X.shape
+    assert y.numel() == n_rows and W.shape[1] == d
+    assert n_rows < 2 ** 31, "row ids are 32-bit"
+    T, K = z_thr.shape
+    assert T == W.shape[0] and K > 0
+    grid = _hip_core.eval_grid(n_rows, d, 0)
+    Wp, thr, n_tiles, n_pass, pt, ph, oc, ot = _curve_buffers(
+        W, z_thr, d, X.device, grid, False)
+    _hip_core.eval_curve_dense(X.data_ptr(), y.data_ptr(), Wp.data_ptr(),
+                               thr.data_ptr(), n_tiles, n_pass, K, n_rows, d,
+                               _xcode(X), pt.data_ptr(), ph.data_ptr(),
+                               oc.data_ptr(), ot.data_ptr(), _stream())
+    return _curve_result(oc, ot, T)
+
+
+def evaluate_curve_csr(indptr, indices, values, y, W, z_thr):
+    _chk(indptr, "indptr", torch.int32)
+    _chk(indices, "indices", torch.int32)
+    _chk(values, "values")
+    _chk(y, "y", torch.float32)
+    n_rows = indptr.shape[0] - 1
+    assert y.numel() == n_rows
+    T, d = W.shape
+    K = z_thr.shape[1]
+    assert z_thr.shape[0] == T and K > 0
+    grid = _hip_core.eval_grid(n_rows, d, 1)
+    Wp, thr, n_tiles, n_pass, pt, ph, oc, ot = _curve_buffers(
+        W, z_thr, d, values.device, grid, True)
+    _hip_core.eval_curve_csr(indptr.data_ptr(), indices.data_ptr(),
+                             values.data_ptr(), y.data_ptr(), Wp.data_ptr(),
+                             thr.data_ptr(), n_tiles, n_pass, K, n_rows, d,
+                             _xcode(values), pt.data_ptr(), ph.data_ptr(),
+                             oc.data_ptr(), ot.data_ptr(), _stream())
+    return _curve_result(oc, ot, T)
+
+
 def evaluate(X, y, W, obj, z_thr):
     """(loss_sum, tp, fp, tn, fn) of the iterates W [T, d] over (X, y)."""
     _chk(X, "X")

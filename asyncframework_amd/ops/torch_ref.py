@@ -239,6 +239,58 @@ def evaluate_csr(indptr: torch.Tensor, indices: torch.Tensor,
     return (loss, *_confusion(Z, yb, z_thr))
 
 
+def _curve_counts(Z: torch.Tensor, y: torch.Tensor, z_thr: torch.Tensor):
+    """Confusion counts of the fp64 scores Z [n, T] at the thresholds
+    z_thr [T, K] (rows non-decreasing): (tp, fp, tn, fn) int64 [T, K] and
+    (n_pos, n_neg) int64 [T]. Predicted positive iff z > thr, so a score
+    exactly on a threshold is below it; a NaN score is below every one."""
+    T, K = z_thr.shape
+    pos = y > 0.5
+    # b = #{k : z > thr[k]} = #{k : thr[k] < z}
+    b = torch.searchsorted(z_thr, Z.t().contiguous(), right=False)  # [T, n]
+    b = torch.where(torch.isnan(Z.t()), torch.zeros_like(b), b)
+    out = []
+    for mask in (pos, ~pos):
+        hist = torch.zeros(T, K + 1, dtype=torch.int64, device=Z.device)
+        hist.scatter_add_(1, b[:, mask],
+                          torch.ones_like(b[:, mask], dtype=torch.int64))
+        # rows with b >= k + 1 are above threshold k
+        above = hist.flip(1).cumsum(1).flip(1)[:, 1:]
+        out.append((above, int(mask.sum()) - above))
+    (tp, fn), (fp, tn) = out
+    full = lambda v: torch.full((T,), int(v), dtype=torch.int64,
+                                device=Z.device)
+    return tp, fp, tn, fn, full(pos.sum()), full((~pos).sum())
+
+
+def evaluate_curve(X: torch.Tensor, y: torch.Tensor, W: torch.Tensor,
+                   z_thr: torch.Tensor, batch_rows: int = 65536):
+    """Reference of the threshold-sweep kernels, fp64 throughout: the
+    counts of _curve_counts for the stacked iterates W [T, d] over the rows
+    of X at the score thresholds z_thr [T, K]."""
+    Wd = W.to(X.device).double()
+    thr = z_thr.to(X.device).double().contiguous()
+    total = None
+    for s in range(0, X.shape[0], batch_rows):
+        part = _curve_counts(X[s:s + batch_rows].double() @ Wd.t(),
+                             y[s:s + batch_rows].double(), thr)
+        total = part if total is None else tuple(
+            a + b for a, b in zip(total, part))
+    return total
+
+
+def evaluate_curve_csr(indptr: torch.Tensor, indices: torch.Tensor,
+                       values: torch.Tensor, y: torch.Tensor,
+                       W: torch.Tensor, z_thr: torch.Tensor):
+    """CSR form of evaluate_curve (fp64 sparse product)."""
+    n_rows = indptr.shape[0] - 1
+    sp = torch.sparse_csr_tensor(indptr, indices, values.double(),
+                                 size=(n_rows, W.shape[1]))
+    Z = torch.sparse.mm(sp, W.to(values.device).double().t())
+    return _curve_counts(Z, y.double(),
+                         z_thr.to(values.device).double().contiguous())
+
+
 def penalty(W: torch.Tensor, objective: str, l2: float,
             l1: float) -> torch.Tensor:
     """Elastic-net term of the REPORTED objective, per stacked iterate, fp64:

@@ -197,14 +197,20 @@ def final_report(cfg: EngineConfig, res: RunResult, data, sparse: bool,
 
 def evaluation_report(cfg: EngineConfig, res: RunResult, test_data,
                       sparse: bool, device: str = "cpu",
-                      threshold: Optional[float] = None) -> None:
+                      threshold: Optional[float] = None,
+                      curve_bins: int = 0) -> None:
     """Held-out block after the epilogue: loss and accuracy of every logged
     iterate on rows the run never trained on (ops.evaluate[_csr]: the fused
-    kernels on a GPU, the fp64 reference on the CPU)."""
+    kernels on a GPU, the fp64 reference on the CPU). curve_bins > 0 adds a
+    second block: areas under the ROC and PR curves and the best F1 of every
+    iterate from a curve_bins-point threshold sweep
+    (ops.evaluate_curve[_csr])."""
     y = test_data[-1]
     n = int(y.shape[0])
     if not res.opt_vars:
         logfmt.evaluation_lines(n, [])
+        if curve_bins > 0:
+            logfmt.curve_lines(curve_bins, [])
         return
     W = torch.stack([w for (_, w) in res.opt_vars]).to(device)
     if sparse:
@@ -217,3 +223,19 @@ def evaluation_report(cfg: EngineConfig, res: RunResult, test_data,
     logfmt.evaluation_lines(
         n, ((t_ms, float(l), float(a)) for (t_ms, _), l, a
             in zip(res.opt_vars, ev.loss, ev.accuracy)))
+    if curve_bins <= 0:
+        return
+    if sparse:
+        cv = ops.evaluate_curve_csr(indptr, indices, values, y, W,
+                                    cfg.objective, num_bins=curve_bins)
+    else:
+        cv = ops.evaluate_curve(X, y, W, cfg.objective, num_bins=curve_bins)
+    f1, best = cv.f_measure(1.0).max(dim=1)
+    z_best = cv.z_thr.gather(1, best[:, None])[:, 0]
+    # the threshold in the user's units: a probability for logistic
+    thr = torch.sigmoid(z_best) if cfg.objective == "logistic" else z_best
+    logfmt.curve_lines(
+        curve_bins, ((t_ms, float(a), float(p), float(f), float(t))
+                     for (t_ms, _), a, p, f, t
+                     in zip(res.opt_vars, cv.auc_roc(), cv.auc_pr(), f1,
+                            thr)))

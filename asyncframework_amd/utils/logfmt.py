@@ -64,3 +64,17 @@ def evaluation_lines(n_rows: int,
     for t_ms, loss, acc in triples:
         print(f"{t_ms},{loss},{acc}")
     print("evaluation finished")
+
+
+def curve_lines(num_bins: int,
+                rows: Iterable[Tuple[int, float, float, float, float]]
+                ) -> None:
+    """Held-out curve block, printed after ``evaluation finished`` when a
+    curve was asked for: the bin count, one
+    ``time_ms,areaUnderROC,areaUnderPR,bestF1,bestF1Threshold`` line per
+    logged iterate (Python float repr; the threshold in the user's units),
+    then ``curve finished``."""
+    print(f"Held-out curve bins: {num_bins}")
+    for t_ms, auc_roc, auc_pr, f1, thr in rows:
+        print(f"{t_ms},{auc_roc},{auc_pr},{f1},{thr}")
+    print("curve finished")

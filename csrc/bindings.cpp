@@ -360,12 +360,13 @@ PYBIND11_MODULE(_hip_core, m) {
 
   // Compiled register / scratch / LDS use and blocks per CU of every
   // evaluation-kernel instantiation, by name.
-  m.def("eval_kernel_info", []() {
+  // `prefix` is "eval_" (K9) or "eval_curve_" (the threshold sweep).
+  auto eval_info = [](int (*query)(int, int*), const std::string& prefix) {
     py::dict out;
     const int n = query_eval_kernel_count();
     for (int k = 0; k < n; ++k) {
       int v[7] = {0};
-      check((hipError_t)query_eval_kernel(k, v), "eval_kernel_info");
+      check((hipError_t)query(k, v), "eval_kernel_info");
       py::dict e;
       e["num_regs"] = v[0];
       e["local_size_bytes"] = v[1];
@@ -374,15 +375,54 @@ PYBIND11_MODULE(_hip_core, m) {
       const std::string xt = v[5] ? "bf16" : "float";
       std::string name;
       if (v[4] == 0)
-        name = "eval_dense_kernel<" + xt + "," + std::to_string(v[6]) + ">";
+        name = "dense_kernel<" + xt + "," + std::to_string(v[6]) + ">";
       else if (v[4] == 1)
-        name = "eval_dense_generic_kernel<" + xt + ">";
+        name = "dense_generic_kernel<" + xt + ">";
       else
-        name = "eval_csr_kernel<" + xt + "," + std::to_string(v[6]) + ">";
-      out[py::str(name)] = e;
+        name = "csr_kernel<" + xt + "," + std::to_string(v[6]) + ">";
+      out[py::str(prefix + name)] = e;
     }
     return out;
+  };
+  m.def("eval_kernel_info",
+        [eval_info]() { return eval_info(query_eval_kernel, "eval_"); });
+  m.def("eval_curve_kernel_info", [eval_info]() {
+    return eval_info(query_eval_curve_kernel, "eval_curve_");
   });
+
+  // Threshold sweep (csrc/eval_curve.h). W as eval_dense / eval_csr; thr is
+  // [n_tiles * eval_tile()][n_pass * eval_curve_tile()] fp64, each row
+  // non-decreasing and +inf past the K real thresholds; part_tot
+  // [grid][2][tile] int64 and part_hist [grid][tile][curve_tile][2] uint32
+  // are per-block scratch; out_cnt is [4][n_tiles * tile][K] int64 (tp, fp,
+  // tn, fn) and out_tot [2][n_tiles * tile] int64 (n_pos, n_neg).
+  m.def("eval_curve_tile", []() { return query_eval_curve_tile(); });
+  m.def("eval_curve_dense",
+        [](uintptr_t X, uintptr_t y, uintptr_t W, uintptr_t thr, int n_tiles,
+           int n_pass, long K, long n_rows, int d, int x_is_bf16,
+           uintptr_t part_tot, uintptr_t part_hist, uintptr_t out_cnt,
+           uintptr_t out_tot, uintptr_t stream) {
+          launch_eval_curve_dense(
+              (const void*)X, (const float*)y, (const float*)W,
+              (const double*)thr, n_tiles, n_pass, K, n_rows, d, x_is_bf16,
+              (long long*)part_tot, (unsigned int*)part_hist,
+              (long long*)out_cnt, (long long*)out_tot, (hipStream_t)stream);
+          check(hipGetLastError(), "eval_curve_dense launch");
+        });
+  m.def("eval_curve_csr",
+        [](uintptr_t indptr, uintptr_t indices, uintptr_t values, uintptr_t y,
+           uintptr_t Wtt, uintptr_t thr, int n_tiles, int n_pass, long K,
+           long n_rows, int d, int v_is_bf16, uintptr_t part_tot,
+           uintptr_t part_hist, uintptr_t out_cnt, uintptr_t out_tot,
+           uintptr_t stream) {
+          launch_eval_curve_csr(
+              (const int*)indptr, (const int*)indices, (const void*)values,
+              (const float*)y, (const float*)Wtt, (const double*)thr, n_tiles,
+              n_pass, K, n_rows, d, v_is_bf16, (long long*)part_tot,
+              (unsigned int*)part_hist, (long long*)out_cnt,
+              (long long*)out_tot, (hipStream_t)stream);
+          check(hipGetLastError(), "eval_curve_csr launch");
+        });
 
   register_libsvm(m);
   register_native_engine(m);

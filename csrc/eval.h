@@ -152,19 +152,19 @@ __device__ __forceinline__ void eval_block_flush(
 // clamped chunk instead of skipping, as pipe_drain does). Each row fragment
 // is read from HBM once per tile and each W fragment from LDS once per
 // EVAL_R rows.
-template <typename XT, int ITERS>
-__global__ __launch_bounds__(EVAL_BLOCK) void eval_dense_kernel(
+//
+// The scoring walks (eval_dense_rows, eval_generic_rows, eval_csr_rows) are
+// shared with the threshold-sweep kernels of eval_curve.h: a walk hands
+// every lane the finished score of its (row slot, iterate) pair as
+// score(z, y, valid), and the kernel around it decides what to count.
+template <typename XT, int ITERS, typename F>
+__device__ __forceinline__ void eval_dense_rows(
     const XT* __restrict__ X, const float* __restrict__ y,
-    const float* __restrict__ Wt, double* __restrict__ part_loss,
-    long long* __restrict__ part_cnt, long n_rows, int d, int objective,
-    double z_thr) {
+    const float* __restrict__ Wt, long n_rows, int d,
+    float* __restrict__ w_lds, F&& score) {
   using RV = RowVec<XT>;
   constexpr int DPAD = ITERS * 256;
   constexpr int NV = EVAL_R * EVAL_TT;
-  static_assert(eval_flush_bytes(EVAL_R) <= EVAL_TT * 256 * sizeof(float),
-                "the flush reuses the tile's LDS");
-  extern __shared__ double eval_smem[];
-  float* w_lds = (float*)eval_smem;  // [EVAL_TT][DPAD]
   for (int i = threadIdx.x; i < EVAL_TT * DPAD; i += EVAL_BLOCK) {
     const int t = i / DPAD, j = i - t * DPAD;
     w_lds[i] = j < d ? Wt[(size_t)t * d + j] : 0.f;
@@ -178,8 +178,7 @@ __global__ __launch_bounds__(EVAL_BLOCK) void eval_dense_kernel(
   const long stride = (long)gridDim.x * EVAL_NW;
   // this lane's (row slot, iterate) pair after reduce_transpose
   const int key = eval_owner_key<NV, WAVE>(lane);
-  const int my_t = key % EVAL_TT, my_r = key / EVAL_TT;
-  EvalAcc acc;
+  const int my_r = key / EVAL_TT;
 
   typename RV::T bufA[EVAL_R][ITERS], bufB[EVAL_R][ITERS];
   float yA[EVAL_R], yB[EVAL_R];
@@ -224,7 +223,7 @@ __global__ __launch_bounds__(EVAL_BLOCK) void eval_dense_kernel(
     float yv = yy[0];
 #pragma unroll
     for (int r = 1; r < EVAL_R; ++r) yv = my_r == r ? yy[r] : yv;
-    acc.add(zz, yv, objective, z_thr, c * EVAL_R + my_r < n_rows);
+    score(zz, yv, c * EVAL_R + my_r < n_rows);
   };
 
   long c = (long)blockIdx.x * EVAL_NW + wave;
@@ -242,12 +241,31 @@ __global__ __launch_bounds__(EVAL_BLOCK) void eval_dense_kernel(
     c += stride;
     __builtin_amdgcn_sched_barrier(0);
   }
+}
+
+template <typename XT, int ITERS>
+__global__ __launch_bounds__(EVAL_BLOCK) void eval_dense_kernel(
+    const XT* __restrict__ X, const float* __restrict__ y,
+    const float* __restrict__ Wt, double* __restrict__ part_loss,
+    long long* __restrict__ part_cnt, long n_rows, int d, int objective,
+    double z_thr) {
+  constexpr int NV = EVAL_R * EVAL_TT;
+  static_assert(eval_flush_bytes(EVAL_R) <= EVAL_TT * 256 * sizeof(float),
+                "the flush reuses the tile's LDS");
+  extern __shared__ double eval_smem[];  // the tile, [EVAL_TT][DPAD] fp32
+  EvalAcc acc;
+  eval_dense_rows<XT, ITERS>(X, y, Wt, n_rows, d, (float*)eval_smem,
+                             [&](float z, float yv, bool valid) {
+                               acc.add(z, yv, objective, z_thr, valid);
+                             });
+  const int wave = threadIdx.x >> 6;
+  const int lane = threadIdx.x & 63;
   // owners: one lane per (slot, iterate); the others hold copies. The tile
   // is dead once every wave is past its last row: its LDS parks the owners
   __syncthreads();
   eval_block_flush<EVAL_R>(acc, (lane & (WAVE / NV - 1)) == 0,
-                           my_r * EVAL_TT + my_t, wave, eval_smem, part_loss,
-                           part_cnt);
+                           eval_owner_key<NV, WAVE>(lane), wave, eval_smem,
+                           part_loss, part_cnt);
 }
 
 // ------------------------------------------ dense fallback, any d (scalar)
@@ -255,17 +273,13 @@ __global__ __launch_bounds__(EVAL_BLOCK) void eval_dense_kernel(
 // aligned and the tile may not fit LDS, so a wave walks one row at a time
 // with element loads (64 consecutive elements per instruction) and reads
 // the W tile through the cache.
-template <typename XT>
-__global__ __launch_bounds__(EVAL_BLOCK) void eval_dense_generic_kernel(
+template <typename XT, typename F>
+__device__ __forceinline__ void eval_generic_rows(
     const XT* __restrict__ X, const float* __restrict__ y,
-    const float* __restrict__ Wt, double* __restrict__ part_loss,
-    long long* __restrict__ part_cnt, long n_rows, int d, int objective,
-    double z_thr) {
+    const float* __restrict__ Wt, long n_rows, int d, F&& score) {
   const int wave = threadIdx.x >> 6;
   const int lane = threadIdx.x & 63;
-  const int my_t = eval_owner_key<EVAL_TT, WAVE>(lane);
   const long stride = (long)gridDim.x * EVAL_NW;
-  EvalAcc acc;
   for (long row = (long)blockIdx.x * EVAL_NW + wave; row < n_rows;
        row += stride) {
     const XT* xrow = X + (size_t)row * d;
@@ -278,11 +292,27 @@ __global__ __launch_bounds__(EVAL_BLOCK) void eval_dense_generic_kernel(
       for (int t = 0; t < EVAL_TT; ++t) z[t] += xv * Wt[(size_t)t * d + j];
     }
     const float zz = reduce_transpose<EVAL_TT, WAVE>(z, lane);
-    acc.add(zz, y[row], objective, z_thr, true);
+    score(zz, y[row], true);
   }
+}
+
+template <typename XT>
+__global__ __launch_bounds__(EVAL_BLOCK) void eval_dense_generic_kernel(
+    const XT* __restrict__ X, const float* __restrict__ y,
+    const float* __restrict__ Wt, double* __restrict__ part_loss,
+    long long* __restrict__ part_cnt, long n_rows, int d, int objective,
+    double z_thr) {
+  EvalAcc acc;
+  eval_generic_rows<XT>(X, y, Wt, n_rows, d,
+                        [&](float z, float yv, bool valid) {
+                          acc.add(z, yv, objective, z_thr, valid);
+                        });
+  const int wave = threadIdx.x >> 6;
+  const int lane = threadIdx.x & 63;
   __shared__ double scratch[eval_flush_bytes(1) / sizeof(double)];
-  eval_block_flush<1>(acc, (lane & (WAVE / EVAL_TT - 1)) == 0, my_t, wave,
-                      scratch, part_loss, part_cnt);
+  eval_block_flush<1>(acc, (lane & (WAVE / EVAL_TT - 1)) == 0,
+                      eval_owner_key<EVAL_TT, WAVE>(lane), wave, scratch,
+                      part_loss, part_cnt);
 }
 
 // --------------------------------------------------------------------- CSR
@@ -291,22 +321,18 @@ __global__ __launch_bounds__(EVAL_BLOCK) void eval_dense_generic_kernel(
 // indices[p] gather brings the EVAL_TT contiguous weights of that column
 // (two 16-byte loads) for every iterate of the tile, and a bf16 value is
 // widened in a register, never expanded in memory.
-template <typename VT, int LPR>
-__global__ __launch_bounds__(EVAL_BLOCK) void eval_csr_kernel(
+template <typename VT, int LPR, typename F>
+__device__ __forceinline__ void eval_csr_rows(
     const int* __restrict__ indptr, const int* __restrict__ indices,
     const VT* __restrict__ values, const float* __restrict__ y,
-    const float* __restrict__ Wtt, double* __restrict__ part_loss,
-    long long* __restrict__ part_cnt, long n_rows, int objective,
-    double z_thr) {
+    const float* __restrict__ Wtt, long n_rows, F&& score) {
   static_assert(LPR >= EVAL_TT && EVAL_TT == 8, "two float4 per column");
   constexpr int NSUB = WAVE / LPR;
   const int wave = threadIdx.x >> 6;
   const int lane = threadIdx.x & 63;
   const int sub = lane / LPR;
   const int sl = lane % LPR;
-  const int my_t = eval_owner_key<EVAL_TT, LPR>(sl);
   const long stride = (long)gridDim.x * EVAL_NW * NSUB;
-  EvalAcc acc;
   // every sub-wave of a wave runs the same number of trips (the shuffles
   // want all 64 lanes): a sub-wave past the end scores nothing
   for (long base = ((long)blockIdx.x * EVAL_NW + wave) * NSUB; base < n_rows;
@@ -332,12 +358,30 @@ __global__ __launch_bounds__(EVAL_BLOCK) void eval_csr_kernel(
       z[4] += v * b.x; z[5] += v * b.y; z[6] += v * b.z; z[7] += v * b.w;
     }
     const float zz = reduce_transpose<EVAL_TT, LPR>(z, sl);
-    acc.add(zz, yv, objective, z_thr, valid);
+    score(zz, yv, valid);
   }
+}
+
+template <typename VT, int LPR>
+__global__ __launch_bounds__(EVAL_BLOCK) void eval_csr_kernel(
+    const int* __restrict__ indptr, const int* __restrict__ indices,
+    const VT* __restrict__ values, const float* __restrict__ y,
+    const float* __restrict__ Wtt, double* __restrict__ part_loss,
+    long long* __restrict__ part_cnt, long n_rows, int objective,
+    double z_thr) {
+  constexpr int NSUB = WAVE / LPR;
+  EvalAcc acc;
+  eval_csr_rows<VT, LPR>(indptr, indices, values, y, Wtt, n_rows,
+                         [&](float z, float yv, bool valid) {
+                           acc.add(z, yv, objective, z_thr, valid);
+                         });
+  const int wave = threadIdx.x >> 6;
+  const int sub = (threadIdx.x & 63) / LPR;
+  const int sl = threadIdx.x % LPR;
   __shared__ double scratch[eval_flush_bytes(NSUB) / sizeof(double)];
   eval_block_flush<NSUB>(acc, (sl & (LPR / EVAL_TT - 1)) == 0,
-                         sub * EVAL_TT + my_t, wave, scratch, part_loss,
-                         part_cnt);
+                         sub * EVAL_TT + eval_owner_key<EVAL_TT, LPR>(sl),
+                         wave, scratch, part_loss, part_cnt);
 }
 
 // Fixed-order sum over the blocks' partials: thread t adds block 0..G-1.
@@ -391,6 +435,77 @@ static void with_xt(int is_bf16, F&& f) {
   if (is_bf16) f(__hip_bfloat16{});
   else f(float{});
 }
+
+// Compiled resource use of instantiation `idx` (0..EVAL_N_KERNELS-1) of a
+// kernel family: dense pipelined [xt][iters] first, then the two generic,
+// then the CSR ones. FAM names the family's three kernel templates and the
+// dynamic LDS its dense kernel takes on top of the W tile (EvalK9 here,
+// EvalCurve in eval_curve.h). out = {numRegs, localSizeBytes (scratch),
+// static + dynamic LDS bytes, max active blocks per CU, kind, xt, shape}.
+#define EVAL_N_KERNELS (16 + 2 + 2)
+template <typename FAM>
+static int eval_query_kernel(int idx, int* out) {
+  const void* fn = nullptr;
+  size_t dyn = 0;
+  int kind = 0, bf = 0, shape = 0;
+  if (idx < 16) {
+    bf = idx / 8;
+    shape = idx % 8 + 1;
+    dyn = eval_lds_bytes(shape) + FAM::extra_lds;
+    with_xt(bf, [&](auto xt) {
+      with_const<1, 2, 3, 4, 5, 6, 7, 8>(shape, [&](auto IT) {
+        fn = FAM::template dense<decltype(xt), decltype(IT)::value>();
+      });
+    });
+  } else if (idx < 18) {
+    kind = 1;
+    bf = idx - 16;
+    with_xt(bf, [&](auto xt) {
+      fn = FAM::template generic<decltype(xt)>();
+    });
+  } else if (idx < EVAL_N_KERNELS) {
+    kind = 2;
+    bf = idx - 18;
+    shape = eval_csr_lpr();
+    with_xt(bf, [&](auto vt) {
+      with_const<16, 32>(shape, [&](auto L) {
+        fn = FAM::template csr<decltype(vt), decltype(L)::value>();
+      });
+    });
+  } else {
+    return -1;
+  }
+  hipFuncAttributes attr;
+  hipError_t e = hipFuncGetAttributes(&attr, fn);
+  int nb = 0;
+  if (e == hipSuccess)
+    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, EVAL_BLOCK,
+                                                     dyn);
+  if (e != hipSuccess) return (int)e;
+  out[0] = attr.numRegs;
+  out[1] = (int)attr.localSizeBytes;
+  out[2] = (int)(attr.sharedSizeBytes + dyn);
+  out[3] = nb;
+  out[4] = kind;
+  out[5] = bf;
+  out[6] = shape;
+  return 0;
+}
+struct EvalK9 {
+  static constexpr size_t extra_lds = 0;
+  template <typename XT, int ITERS>
+  static const void* dense() {
+    return (const void*)eval_dense_kernel<XT, ITERS>;
+  }
+  template <typename XT>
+  static const void* generic() {
+    return (const void*)eval_dense_generic_kernel<XT>;
+  }
+  template <typename VT, int LPR>
+  static const void* csr() {
+    return (const void*)eval_csr_kernel<VT, LPR>;
+  }
+};
 
 extern "C" {
 
@@ -462,58 +577,8 @@ void launch_eval_csr(const int* indptr, const int* indices,
   }
 }
 
-// Compiled resource use of evaluation-kernel instantiation `idx`
-// (0..EVAL_N_KERNELS-1): dense pipelined [xt][iters] first, then the two
-// generic, then the CSR ones. out = {numRegs, localSizeBytes (scratch),
-// static + dynamic LDS bytes, max active blocks per CU, kind, xt, shape}.
-#define EVAL_N_KERNELS (16 + 2 + 2)
 int query_eval_kernel(int idx, int* out) {
-  const void* fn = nullptr;
-  size_t dyn = 0;
-  int kind = 0, bf = 0, shape = 0;
-  if (idx < 16) {
-    bf = idx / 8;
-    shape = idx % 8 + 1;
-    dyn = eval_lds_bytes(shape);
-    with_xt(bf, [&](auto xt) {
-      with_const<1, 2, 3, 4, 5, 6, 7, 8>(shape, [&](auto IT) {
-        fn = (const void*)
-            eval_dense_kernel<decltype(xt), decltype(IT)::value>;
-      });
-    });
-  } else if (idx < 18) {
-    kind = 1;
-    bf = idx - 16;
-    with_xt(bf, [&](auto xt) {
-      fn = (const void*)eval_dense_generic_kernel<decltype(xt)>;
-    });
-  } else if (idx < EVAL_N_KERNELS) {
-    kind = 2;
-    bf = idx - 18;
-    shape = eval_csr_lpr();
-    with_xt(bf, [&](auto vt) {
-      with_const<16, 32>(shape, [&](auto L) {
-        fn = (const void*)eval_csr_kernel<decltype(vt), decltype(L)::value>;
-      });
-    });
-  } else {
-    return -1;
-  }
-  hipFuncAttributes attr;
-  hipError_t e = hipFuncGetAttributes(&attr, fn);
-  int nb = 0;
-  if (e == hipSuccess)
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, EVAL_BLOCK,
-                                                     dyn);
-  if (e != hipSuccess) return (int)e;
-  out[0] = attr.numRegs;
-  out[1] = (int)attr.localSizeBytes;
-  out[2] = (int)(attr.sharedSizeBytes + dyn);
-  out[3] = nb;
-  out[4] = kind;
-  out[5] = bf;
-  out[6] = shape;
-  return 0;
+  return eval_query_kernel<EvalK9>(idx, out);
 }
 int query_eval_kernel_count() { return EVAL_N_KERNELS; }
 

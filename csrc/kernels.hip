@@ -27,6 +27,9 @@
 //   K9 eval.h          — fused held-out evaluation: loss sum + confusion
 //                        counts of a tile of stacked iterates in one pass
 //                        over the rows (included at the end of this file).
+//   K10 eval_curve.h   — K9's scoring with a threshold histogram per
+//                        iterate: the confusion counts at EVAL_KT thresholds
+//                        (ROC / PR points) from the same single pass.
 // The link function of K1-K3 (lsq / logistic / hinge) lives in link.h.
 // Launchers: runtime (dtype, saga, ITERS, DEPTH, LPR, flags) become template
 // arguments through with_const / with_bool / with_xt_saga / with_pipe_shape.
@@ -1960,3 +1963,8 @@ void launch_alpha_gather(float* a_dst, const float* a_src, const int* rows,
 // Fused held-out evaluation kernels and their launchers: built on the row
 // machinery (RowVec, row_rsrc, cvt4, to_f32) and the with_const helper above.
 #include "eval.h"
+
+// ---------------------------------------------------------------- K10
+// Threshold sweep of the evaluation (ROC / PR points in one pass): the K9
+// scoring walks with an LDS histogram per iterate.
+#include "eval_curve.h"

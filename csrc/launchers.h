@@ -194,4 +194,26 @@ void launch_eval_csr(const int* indptr, const int* indices,
 int query_eval_kernel(int idx, int* out);
 int query_eval_kernel_count();
 
+// ---- threshold sweep of the evaluation (defined in eval_curve.h) --------
+
+int query_eval_curve_tile();
+
+void launch_eval_curve_dense(const void* X, const float* y, const float* W,
+                             const double* thr, int n_tiles, int n_pass,
+                             long K, long n_rows, int d, int x_is_bf16,
+                             long long* part_tot, unsigned int* part_hist,
+                             long long* out_cnt, long long* out_tot,
+                             hipStream_t stream);
+
+void launch_eval_curve_csr(const int* indptr, const int* indices,
+                           const void* values, const float* y,
+                           const float* Wtt, const double* thr, int n_tiles,
+                           int n_pass, long K, long n_rows, int d,
+                           int v_is_bf16, long long* part_tot,
+                           unsigned int* part_hist, long long* out_cnt,
+                           long long* out_tot, hipStream_t stream);
+
+// as query_eval_kernel, query_eval_kernel_count() instantiations
+int query_eval_curve_kernel(int idx, int* out);
+
 }  // extern "C"
