@@ -54,13 +54,34 @@ def _xcode(X: torch.Tensor) -> int:
     raise TypeError(f"X dtype must be fp32 or bf16, got {X.dtype}")
 
 
+CU_LDS_BYTES = 163840  # one CU's LDS (csrc/kernels.hip)
+
+
+def _chk_row_start(row_start) -> None:
+    # the kernels take the Philox block of a row as (row_start + i) / 4
+    assert row_start % 4 == 0, "shard starts must be 4-aligned (philox block)"
+
+
+def _chk_dense_lds(d: int) -> None:
+    """The generic dense kernel (d > 2048, d % 4 != 0 or ASYNCAMD_NO_PIPE=1)
+    keeps w and one gradient slab per sub-wave in LDS; past one CU's LDS it
+    cannot launch."""
+    pipe, lpr, lds = _hip_core.dense_launch_form(int(d))
+    if not pipe and lds > CU_LDS_BYTES:
+        raise ValueError(
+            f"dense gradient at d={d}: the generic kernel needs {lds} bytes "
+            f"of LDS at {lpr} lanes per row, over the limit of "
+            f"{CU_LDS_BYTES} bytes per workgroup")
+
+
 def grad_dense(X, y, w, out, seed, round_k, row_start, rate, obj) -> int:
     _chk(X, "X")
-    assert row_start % 4 == 0, "shard starts must be 4-aligned (philox block)" 
+    _chk_row_start(row_start)
     _chk(y, "y", torch.float32)
     _chk(out, "out", torch.float32)
     w = w.float().contiguous()
     n_rows, d = X.shape
+    _chk_dense_lds(d)
     n_ctr = torch.zeros(1, dtype=torch.int32, device=X.device)
     _hip_core.grad_dense(X.data_ptr(), y.data_ptr(), w.data_ptr(),
                          out.data_ptr(), 0, n_ctr.data_ptr(), 0, n_rows, d,
@@ -72,6 +93,7 @@ def grad_dense(X, y, w, out, seed, round_k, row_start, rate, obj) -> int:
 
 def grad_csr(indptr, indices, values, y, w, out, seed, round_k, row_start,
              rate, obj) -> int:
+    _chk_row_start(row_start)
     _chk(indptr, "indptr", torch.int32)
     _chk(indices, "indices", torch.int32)
     _chk(values, "values")
@@ -91,11 +113,12 @@ def grad_csr(indptr, indices, values, y, w, out, seed, round_k, row_start,
 def saga_grad_dense(X, y, w, alpha, g, seed, round_k, row_start, rate, obj
                     ) -> Tuple[torch.Tensor, torch.Tensor]:
     _chk(X, "X")
-    assert row_start % 4 == 0, "shard starts must be 4-aligned (philox block)" 
+    _chk_row_start(row_start)
     _chk(alpha, "alpha", torch.float32)
     _chk(g, "g", torch.float32)
     w = w.float().contiguous()
     n_rows, d = X.shape
+    _chk_dense_lds(d)
     cap = n_rows if rate >= 1.0 else min(n_rows,
                                          int(rate * n_rows * 2) + 4096)
     idx = torch.empty(cap, dtype=torch.int32, device=X.device)
@@ -113,6 +136,7 @@ def saga_grad_dense(X, y, w, alpha, g, seed, round_k, row_start, rate, obj
 
 def saga_grad_csr(indptr, indices, values, y, w, alpha, g, seed, round_k,
                   row_start, rate, obj) -> Tuple[torch.Tensor, torch.Tensor]:
+    _chk_row_start(row_start)
     _chk(indptr, "indptr", torch.int32)
     _chk(alpha, "alpha", torch.float32)
     _chk(g, "g", torch.float32)
@@ -157,6 +181,7 @@ def spill_refresh(alpha_dev, alpha_pinned, y, rowlist, ylist, cnt, cap, *,
     device row list, then gather ONLY those entries from the pinned master
     into the device staging table — ~1% of the table instead of all of it,
     fully async on the current stream."""
+    _chk_row_start(row_start)
     _chk(alpha_dev, "alpha_dev", torch.float32)
     assert alpha_pinned.is_pinned() and alpha_pinned.dtype == torch.float32
     cnt.zero_()

@@ -202,16 +202,27 @@ PYBIND11_MODULE(_hip_core, m) {
   // What a dense gradient launch at feature dim d will run (the launchers'
   // own shape selection, csrc/kernels.hip): template parameters, compiled
   // register/scratch use and the occupancy the runtime computes for them.
+  // A solo launch that takes the generic form (d > 2048, d % 4 != 0 or
+  // ASYNCAMD_NO_PIPE=1) reports {kernel, lpr, dynamic_lds_bytes} only.
   m.def("dense_kernel_info", [](int d, int x_is_bf16, int saga, int wave) {
+    py::dict out;
+    long long form[3] = {0};
+    query_dense_launch(d, form);
+    if (!wave && d > 0 && !form[0]) {
+      out["kernel"] = "grad_dense_kernel";
+      out["lpr"] = (int)form[1];
+      out["dynamic_lds_bytes"] = form[2];
+      return out;
+    }
     int v[8] = {0};
     const int rc = query_dense_kernel(d, x_is_bf16, saga, wave, v);
     if (rc == -1)
       throw std::runtime_error(
-          "dense_kernel_info: d must be a multiple of 4 in [4, 2048] (other "
-          "dims run the generic grad_dense_kernel)");
+          "dense_kernel_info: d must be a multiple of 4 in [4, 2048] (wave "
+          "launches have no generic form)");
     check((hipError_t)rc, "dense_kernel_info");
-    py::dict out;
     out["kernel"] = wave ? "grad_dense_wave_kernel" : "grad_dense_pipe_kernel";
+    out["lpr"] = 64;
     out["iters"] = v[0];
     out["depth"] = v[1];
     out["waves_per_simd_hint"] = v[2];
@@ -219,6 +230,24 @@ PYBIND11_MODULE(_hip_core, m) {
     out["local_size_bytes"] = v[4];
     out["dynamic_lds_bytes"] = v[5];
     out["max_active_blocks_per_cu"] = v[6];
+    return out;
+  });
+
+  // (pipelined?, lanes per row, generic-form dynamic LDS bytes) of a solo
+  // dense launch at feature dim d, overrides included. No runtime call: the
+  // Python wrappers check the LDS need with it before every launch.
+  m.def("dense_launch_form", [](int d) {
+    long long form[3] = {0};
+    query_dense_launch(d, form);
+    return py::make_tuple(form[0] != 0, (int)form[1], form[2]);
+  });
+
+  // What a CSR gradient launch will run: the lanes per row that
+  // ASYNCAMD_CSR_LPR selects (an unrecognised value runs the default).
+  m.def("csr_kernel_info", []() {
+    py::dict out;
+    out["kernel"] = "grad_csr_kernel";
+    out["lpr"] = query_csr_lpr();
     return out;
   });
 

@@ -1470,6 +1470,17 @@ static inline int csr_lpr() {
   return (v == 8 || v == 16 || v == 32 || v == 64) ? v : 32;
 }
 
+// Which dense form a solo launch at feature dim d takes, and the generic
+// form's dynamic LDS: w_lds[d] + one slab per sub-wave. launch_dense and
+// query_dense_launch both go through these two.
+static inline bool dense_pipe_ok(int d) {
+  const char* np = std::getenv("ASYNCAMD_NO_PIPE");  // re-read: sweeps
+  return (d % 4 == 0) && (d <= 2048) && !(np && np[0] == '1');
+}
+static inline size_t dense_generic_lds_bytes(int d, int lpr) {
+  return (size_t)(1 + WAVES_PER_BLOCK * (WAVE / lpr)) * d * sizeof(float);
+}
+
 // The one dense launch: the four extern "C" entry points below differ only
 // in which arguments they leave null.
 static void launch_dense(const void* X, const float* y, const float* w,
@@ -1485,8 +1496,7 @@ static void launch_dense(const void* X, const float* y, const float* w,
   const uint32_t thr = philox_threshold(rate);
   const int take_all = rate >= 1.0;
   const int grid = grad_grid(n_rows);
-  const char* np = std::getenv("ASYNCAMD_NO_PIPE");
-  const bool pipe_ok = (d % 4 == 0) && (d <= 2048) && !(np && np[0] == '1');
+  const bool pipe_ok = dense_pipe_ok(d);
   with_xt_saga_obj(x_is_bf16, saga, objective, [&](auto xt, auto sg,
                                                    auto hg) {
     using XT = decltype(xt);
@@ -1508,7 +1518,7 @@ static void launch_dense(const void* X, const float* y, const float* w,
       return;
     }
     const int lpr = pick_lpr(d);
-    const size_t smem = (size_t)(1 + 4 * (WAVE / lpr)) * d * sizeof(float);
+    const size_t smem = dense_generic_lds_bytes(d, lpr);
     with_const<16, 32, 64>(lpr, [&](auto L) {
       hipLaunchKernelGGL((grad_dense_kernel<XT, SG, decltype(L)::value, HG>),
                          dim3(grid), dim3(BLOCK), smem, stream, (const XT*)X,
@@ -1704,6 +1714,22 @@ int query_dense_kernel(int d, int x_is_bf16, int saga, int wave, int* out) {
   });
   return rc;
 }
+
+// Which form a solo dense launch (launch_dense) at feature dim d takes right
+// now, overrides included: out = {1 pipelined / 0 generic, lanes per row
+// (the pipelined form's rows are whole waves: 64), the generic form's
+// dynamic LDS bytes (0 for the pipelined form: query_dense_kernel has it)}.
+// Host only: no runtime call.
+void query_dense_launch(int d, long long* out) {
+  const bool pipe = dense_pipe_ok(d);
+  const int lpr = pipe ? WAVE : pick_lpr(d);
+  out[0] = pipe ? 1 : 0;
+  out[1] = lpr;
+  out[2] = pipe ? 0 : (long long)dense_generic_lds_bytes(d, lpr);
+}
+
+// The lanes per row a CSR launch (solo or wave) takes right now.
+int query_csr_lpr() { return csr_lpr(); }
 
 void launch_scan_rows_wave(const void* slots_dev, const void* cmd_host,
                            uint64_t seed, double rate, hipStream_t stream) {

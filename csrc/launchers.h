@@ -70,6 +70,10 @@ void launch_grad_dense_wave(const void* slots_dev, const void* cmd_host,
 // out[8], see the definition
 int query_dense_kernel(int d, int x_is_bf16, int saga, int wave, int* out);
 
+// out[3], see the definition
+void query_dense_launch(int d, long long* out);
+int query_csr_lpr();
+
 void launch_scan_rows_wave(const void* slots_dev, const void* cmd_host,
                            uint64_t seed, double rate, hipStream_t stream);
 

@@ -158,7 +158,8 @@ def test_saga_csr_hinge_matches_ref(scale):
     _require_hip()
     indptr, indices, values, y, w = _csr_case(2000, 300, 20, scale, seed=9)
     n = y.numel()
-    alpha = torch.zeros(n, device="cuda")
+    alpha = torch.randn(n, device="cuda",
+                        generator=torch.Generator(device="cuda").manual_seed(8))
     g, idx, e, cnt = ops.saga_grad_csr(indptr, indices, values, y, w, alpha,
                                        seed=31, round_k=2, row_start=100,
                                        rate=0.3, objective="hinge")

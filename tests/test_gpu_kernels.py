@@ -128,7 +128,8 @@ def test_saga_csr_matches_ref():
                                                device="cuda")
     w = torch.randn(d, device="cuda",
                     generator=torch.Generator(device="cuda").manual_seed(10))
-    alpha = torch.zeros(n, device="cuda")
+    alpha = torch.randn(n, device="cuda",
+                        generator=torch.Generator(device="cuda").manual_seed(11))
     g, idx, e, cnt = ops.saga_grad_csr(indptr, indices, values, y, w, alpha,
                                        seed=31, round_k=2, row_start=100,
                                        rate=0.3)
