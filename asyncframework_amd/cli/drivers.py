@@ -5,7 +5,7 @@ Positional args (13) exactly as the reference drivers parse them
 [num rows] [num partitions] [num iterations] [step size] [taw] [batch rate]
 [bucket ratio] [printer freq] [coeff] [seed]; the MLlib baseline takes 8
 (SparkSGDMLLIB.scala:30-37). Extra engine flags (--device, --dtype,
---objective, --sparse, --history-placement, --test-file / --test-rows /
+--objective, --sparse, --history-placement, --standardize, --test-file / --test-rows /
 --threshold / --curve-bins for a held-out evaluation) come after the
 positionals.
 
@@ -91,6 +91,11 @@ def _engine_flags(p: argparse.ArgumentParser) -> None:
                         "the ROC and PR curves and the best F1 of every "
                         "logged iterate, from a threshold sweep of this "
                         "many points (0 = off)")
+    p.add_argument("--standardize", action="store_true",
+                   help="scale every feature to unit variance before "
+                        "training (std only, no centring: MLlib's "
+                        "useFeatureScaling); held-out rows take the "
+                        "training scaler")
     p.add_argument("--resume-from", default="",
                    help="restore optimizer state from a checkpoint file "
                         "before running")
@@ -147,6 +152,12 @@ def _load(cfg: EngineConfig, a, sparse: bool, device: str):
     return data, test
 
 
+def _standardize(cfg: EngineConfig, a, data, test_data, sparse: bool
+                 ) -> None:
+    if getattr(a, "standardize", False):
+        runner.standardize_(data, test_data, sparse, d=cfg.d)
+
+
 def _evaluate(cfg: EngineConfig, a, res, test_data, sparse: bool,
               device: str) -> None:
     if test_data is not None:
@@ -165,6 +176,7 @@ def _run(cfg: EngineConfig, a, app: str, names, vals) -> None:
     logfmt.print_header(app, names, vals)
     sparse = a.sparse
     data, test_data = _load(cfg, a, sparse, a.device)
+    _standardize(cfg, a, data, test_data, sparse)
     if sparse:
         workers = runner.build_csr_workers(cfg, *data)
     else:
@@ -204,6 +216,7 @@ def _run_dist(cfg: EngineConfig, a, app: str, names, vals,
         logfmt.print_header(app, names, vals)
     sparse = a.sparse
     data, test_data = _load(cfg, a, sparse, "cpu")
+    _standardize(cfg, a, data, test_data, sparse)
     shards = row_shards(cfg.N, cfg.num_workers)
     workers = []
     for j in range(M):
@@ -309,6 +322,7 @@ def sgd_mllib(argv: Optional[List[str]] = None) -> None:
         return
     logfmt.print_header("MLlib SGD", ARG_NAMES_8, vals)
     data, test_data = _load(cfg, a, a.sparse, a.device)
+    _standardize(cfg, a, data, test_data, a.sparse)
     if a.sparse:
         workers = runner.build_csr_workers(cfg, *data)
     else:

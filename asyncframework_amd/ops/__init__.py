@@ -568,3 +568,124 @@ def evaluate_csr(indptr: torch.Tensor, indices: torch.Tensor,
     return _eval_result(
         torch_ref.evaluate_csr(indptr, indices, values, y, W, objective,
                                z_thr), n_rows, N_total)
+
+
+class ColStats(NamedTuple):
+    """Per-column summary of a data matrix (MLlib Statistics.colStats /
+    MultivariateOnlineSummarizer): ``count`` rows; ``mean``, ``m2`` =
+    sum (x - mean)^2, ``min``, ``max``, ``norm_l1`` = sum |x| and ``sumsq`` =
+    sum x^2 in fp64 [d]; ``num_nonzeros`` int64 [d]. For CSR data the
+    implicit zeros count towards count, mean, m2, min and max."""
+    count: int
+    mean: torch.Tensor
+    m2: torch.Tensor
+    num_nonzeros: torch.Tensor
+    min: torch.Tensor
+    max: torch.Tensor
+    norm_l1: torch.Tensor
+    sumsq: torch.Tensor
+
+    @property
+    def variance(self) -> torch.Tensor:
+        """m2 / (count - 1), MLlib's unbiased form; 0 for count <= 1."""
+        if self.count <= 1:
+            return torch.zeros_like(self.m2)
+        return self.m2 / (self.count - 1)
+
+    @property
+    def std(self) -> torch.Tensor:
+        return self.variance.sqrt()
+
+    @property
+    def norm_l2(self) -> torch.Tensor:
+        return self.sumsq.sqrt()
+
+    def merge(self, other: "ColStats") -> "ColStats":
+        """The summary of both row sets together (shards, a file read in
+        chunks): the pairwise update of Chan et al. on (count, mean, m2),
+        as the kernels merge their partials, on the host. A column that
+        holds one value overall gets m2 == 0 exactly."""
+        na, nb = self.count, other.count
+        if nb == 0:
+            return self
+        if na == 0:
+            return other
+        o = ColStats(nb, *(t.to(self.mean.device) for t in other[1:]))
+        n = na + nb
+        delta = o.mean - self.mean
+        mean = self.mean + delta * (nb / n)
+        m2 = self.m2 + o.m2 + delta * delta * (na * nb / n)
+        mn = torch.minimum(self.min, o.min)
+        mx = torch.maximum(self.max, o.max)
+        m2 = torch.where(mn == mx, torch.zeros_like(m2), m2)
+        return ColStats(n, mean, m2, self.num_nonzeros + o.num_nonzeros, mn,
+                        mx, self.norm_l1 + o.norm_l1, self.sumsq + o.sumsq)
+
+
+def _col_stats_zeros(d: int, device) -> ColStats:
+    z = lambda: torch.zeros(d, dtype=torch.float64, device=device)
+    return ColStats(0, z(), z(), torch.zeros(d, dtype=torch.int64,
+                                             device=device),
+                    z(), z(), z(), z())
+
+
+def col_stats(X: torch.Tensor) -> ColStats:
+    """Column statistics of X [n, d] from one pass over it (K11,
+    csrc/col_stats.h): fp64 accumulation about a per-column pivot, partials
+    merged in a fixed order, so two calls are bit-identical and a constant
+    column has m2 == 0 exactly. bf16 data is never expanded in memory. CPU
+    tensors take the fp64 two-pass reference. Zero rows: zeros, with
+    min = max = 0, without a launch."""
+    if X.dim() != 2:
+        raise ValueError(f"X must be [n, d], got {tuple(X.shape)}")
+    n, d = X.shape
+    if n == 0 or d == 0:
+        return _col_stats_zeros(d, X.device)
+    if X.is_cuda:
+        mod = _require_hip("col_stats")
+        if mod is not None:
+            return ColStats(n, *mod.col_stats(X))
+    return ColStats(n, *torch_ref.col_stats(X))
+
+
+def col_stats_csr(indptr: torch.Tensor, indices: torch.Tensor,
+                  values: torch.Tensor, d: int) -> ColStats:
+    """CSR form of col_stats. On a GPU the sums over the non-zeros are fp64
+    atomic adds: mean, m2, norm_l1 and sumsq are reproducible to the fp64
+    summation bound (nnz_j * 2^-52 * sum |term|), not bitwise;
+    num_nonzeros, min and max are exact, and a column that holds one value
+    (implicit zeros included) has m2 == 0 exactly."""
+    n = indptr.shape[0] - 1
+    if n <= 0 or d == 0:
+        return _col_stats_zeros(d, values.device)
+    if values.is_cuda:
+        mod = _require_hip("col_stats_csr")
+        if mod is not None:
+            return ColStats(n, *mod.col_stats_csr(indptr, indices, values,
+                                                  int(d)))
+    return ColStats(n, *torch_ref.col_stats_csr(indptr, indices, values,
+                                                int(d)))
+
+
+def scale_(X: torch.Tensor, mean: torch.Tensor, factor: torch.Tensor, *,
+           with_mean: bool = False) -> None:
+    """X <- (X - mean) * factor per column, in place: fp32 arithmetic,
+    rounded once to X's type. ``mean`` and ``factor`` are fp32 [d]; without
+    ``with_mean`` the mean is not read."""
+    if X.is_cuda:
+        mod = _require_hip("scale_")
+        if mod is not None:
+            mod.scale_(X, mean, factor, with_mean)
+            return
+    torch_ref.scale_(X, mean, factor, with_mean)
+
+
+def scale_csr_(indices: torch.Tensor, values: torch.Tensor,
+               factor: torch.Tensor) -> None:
+    """values <- values * factor[indices], in place (fp32, rounded once)."""
+    if values.is_cuda:
+        mod = _require_hip("scale_csr_")
+        if mod is not None:
+            mod.scale_csr_(indices, values, factor)
+            return
+    torch_ref.scale_csr_(indices, values, factor)

@@ -330,3 +330,88 @@ def evaluate_csr(indptr, indices, values, y, W, obj, z_thr):
                        pl.data_ptr(), pc.data_ptr(), ol.data_ptr(),
                        oc.data_ptr(), _stream())
     return (ol[:T], oc[0, :T], oc[1, :T], oc[2, :T], oc[3, :T])
+
+
+def _col_stats_out(d, device):
+    out_f64 = torch.empty(6, d, dtype=torch.float64, device=device)
+    out_nnz = torch.empty(d, dtype=torch.int64, device=device)
+    return out_f64, out_nnz
+
+
+def _col_stats_result(out_f64, out_nnz):
+    """(mean, m2, num_nonzeros, min, max, norm_l1, sumsq)."""
+    return (out_f64[0], out_f64[1], out_nnz, out_f64[2], out_f64[3],
+            out_f64[4], out_f64[5])
+
+
+def col_stats(X):
+    """Per-column statistics of X [n, d], n > 0 and d > 0, from one pass
+    (csrc/col_stats.h)."""
+    _chk(X, "X")
+    n_rows, d = X.shape
+    assert n_rows > 0 and d > 0
+    assert n_rows < 2 ** 31, "per-block non-zero counts are 32-bit"
+    bf = _xcode(X)
+    gy = int(_hip_core.col_stats_geom(X.data_ptr(), n_rows, d, bf)["grid_y"])
+    dev = X.device
+    part_f64 = torch.empty(gy * 5 * d, dtype=torch.float64, device=dev)
+    part_mm = torch.empty(gy * 2 * d, dtype=torch.float32, device=dev)
+    part_nnz = torch.empty(gy * d, dtype=torch.int32, device=dev)
+    out_f64, out_nnz = _col_stats_out(d, dev)
+    _hip_core.col_stats_dense(X.data_ptr(), n_rows, d, bf,
+                              part_f64.data_ptr(), part_mm.data_ptr(),
+                              part_nnz.data_ptr(), out_f64.data_ptr(),
+                              out_nnz.data_ptr(), _stream())
+    return _col_stats_result(out_f64, out_nnz)
+
+
+def col_stats_csr(indptr, indices, values, d):
+    _chk(indptr, "indptr", torch.int32)
+    _chk(indices, "indices", torch.int32)
+    _chk(values, "values")
+    n_rows = indptr.shape[0] - 1
+    assert n_rows > 0 and d > 0 and n_rows < 2 ** 31
+    assert indices.numel() == values.numel()
+    dev = values.device
+    sums = torch.empty(3 * d, dtype=torch.float64, device=dev)
+    ints = torch.empty(3 * d, dtype=torch.int32, device=dev)
+    out_f64, out_nnz = _col_stats_out(d, dev)
+    _hip_core.col_stats_csr(indptr.data_ptr(), indices.data_ptr(),
+                            values.data_ptr(), n_rows, d,
+                            int(values.numel()), _xcode(values),
+                            sums.data_ptr(), ints.data_ptr(),
+                            out_f64.data_ptr(), out_nnz.data_ptr(), _stream())
+    return _col_stats_result(out_f64, out_nnz)
+
+
+def _chk_scale_vec(t, name, d, device):
+    _chk(t, name, torch.float32)
+    assert t.numel() == d and t.device == device, \
+        f"{name} must be fp32 [{d}] on {device}"
+
+
+def scale_(X, mean, factor, with_mean) -> None:
+    """X <- ((X - mean) * factor) in fp32, rounded to X's type, in place."""
+    _chk(X, "X")
+    n_rows, d = X.shape
+    if n_rows == 0 or d == 0:
+        return
+    _chk_scale_vec(mean, "mean", d, X.device)
+    _chk_scale_vec(factor, "factor", d, X.device)
+    _hip_core.scale_dense(X.data_ptr(), mean.data_ptr(), factor.data_ptr(),
+                          n_rows, d, _xcode(X), int(bool(with_mean)),
+                          _stream())
+
+
+def scale_csr_(indices, values, factor) -> None:
+    """values <- values * factor[indices] in fp32, rounded, in place."""
+    _chk(indices, "indices", torch.int32)
+    _chk(values, "values")
+    if values.numel() == 0:
+        return
+    assert indices.numel() == values.numel()
+    d = int(factor.numel())
+    _chk_scale_vec(factor, "factor", d, values.device)
+    _hip_core.scale_csr(indices.data_ptr(), values.data_ptr(),
+                        factor.data_ptr(), int(values.numel()), d,
+                        _xcode(values), _stream())

@@ -291,6 +291,73 @@ def evaluate_curve_csr(indptr: torch.Tensor, indices: torch.Tensor,
                          z_thr.to(values.device).double().contiguous())
 
 
+def _const_m2(m2: torch.Tensor, mn: torch.Tensor, mx: torch.Tensor
+              ) -> torch.Tensor:
+    """M2 with exact zeros where the column holds one value: a two-pass mean
+    is sum / n, which need not reproduce that value to the last bit."""
+    return torch.where(mn == mx, torch.zeros_like(m2), m2)
+
+
+def col_stats(X: torch.Tensor):
+    """fp64 two-pass column statistics of X [n, d], n > 0 (MLlib
+    Statistics.colStats): (mean, m2 = sum (x - mean)^2, num_nonzeros int64,
+    min, max, norm_l1 = sum |x|, sumsq = sum x^2), each [d]."""
+    Xd = X.double()
+    mean = Xd.sum(0) / X.shape[0]
+    mn, mx = Xd.min(0).values, Xd.max(0).values
+    m2 = _const_m2(((Xd - mean) ** 2).sum(0), mn, mx)
+    return (mean, m2, (Xd != 0).sum(0), mn, mx, Xd.abs().sum(0),
+            (Xd * Xd).sum(0))
+
+
+def col_stats_csr(indptr: torch.Tensor, indices: torch.Tensor,
+                  values: torch.Tensor, d: int):
+    """CSR form of col_stats with MultivariateOnlineSummarizer semantics:
+    stored zeros are skipped and the implicit zeros count towards n, mean,
+    m2, min and max. Two passes of index_add_ over the non-zeros; nothing is
+    densified."""
+    n = indptr.shape[0] - 1
+    lo, hi = int(indptr[0]), int(indptr[n])
+    v = values[lo:hi].double()
+    j = indices[lo:hi].long()
+    keep = v != 0
+    v, j = v[keep], j[keep]
+    z = lambda: torch.zeros(d, dtype=torch.float64, device=values.device)
+    nnz = torch.zeros(d, dtype=torch.int64, device=values.device)
+    nnz.index_add_(0, j, torch.ones_like(j))
+    mean = z().index_add_(0, j, v) / n
+    within = z().index_add_(0, j, (v - mean[j]) ** 2)
+    m2 = within + (n - nnz).double() * mean * mean
+    inf = torch.full((d,), float("inf"), dtype=torch.float64,
+                     device=values.device)
+    mn = inf.clone().scatter_reduce_(0, j, v, "amin")
+    mx = (-inf).scatter_reduce_(0, j, v, "amax")
+    zeros = nnz < n  # an implicit zero takes part in min and max
+    mn = torch.where(zeros, mn.clamp(max=0.0), mn)
+    mx = torch.where(zeros, mx.clamp(min=0.0), mx)
+    return (mean, _const_m2(m2, mn, mx), nnz, mn, mx,
+            z().index_add_(0, j, v.abs()), z().index_add_(0, j, v * v))
+
+
+def scale_(X: torch.Tensor, mean: torch.Tensor, factor: torch.Tensor,
+           with_mean: bool) -> None:
+    """X <- (X - mean) * factor in fp32 (a subtraction and a multiplication,
+    each rounded), then rounded to X's type, in place; without ``with_mean``
+    X * factor."""
+    Xf = X.float()
+    if with_mean:
+        Xf = Xf - mean.float()
+    X.copy_((Xf * factor.float()).to(X.dtype))
+
+
+def scale_csr_(indices: torch.Tensor, values: torch.Tensor,
+               factor: torch.Tensor) -> None:
+    """values <- values * factor[indices] in fp32, rounded to the values'
+    type, in place."""
+    values.copy_((values.float() * factor.float()[indices.long()])
+                 .to(values.dtype))
+
+
 def penalty(W: torch.Tensor, objective: str, l2: float,
             l1: float) -> torch.Tensor:
     """Elastic-net term of the REPORTED objective, per stacked iterate, fp64:

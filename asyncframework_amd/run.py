@@ -81,6 +81,36 @@ def load_test_dataset(cfg: EngineConfig, pathname: str, *,
                        dense=not sparse, dtype=dt, device=device)
 
 
+def standardize_(data, test_data=None, sparse: bool = False,
+                 d: Optional[int] = None):
+    """Fit a unit-variance scaler (no centring: MLlib's useFeatureScaling)
+    on the training rows and rescale the training rows and, with the SAME
+    scaler, the held-out rows, in place. ``data`` / ``test_data`` are the
+    tuples of load_dataset / load_test_dataset; ``d`` is the number of
+    columns of CSR data (default: the largest column id present, plus one).
+    Returns the ScalerModel; its unscale_weights maps trained weights back
+    to the raw features."""
+    from .data.scale import StandardScaler
+    if sparse:
+        indptr, indices, values, _ = data
+        if d is None:
+            ids = [p[1] for p in (data, test_data)
+                   if p is not None and p[1].numel()]
+            d = max((int(i.max()) + 1 for i in ids), default=0)
+        stats = ops.col_stats_csr(indptr, indices, values, d)
+    else:
+        stats = ops.col_stats(data[0])
+    model = StandardScaler(with_mean=False, with_std=True).fit(stats)
+    for part in (data, test_data):
+        if part is None:
+            continue
+        if sparse:
+            model.transform_csr_(part[1], part[2])
+        else:
+            model.transform_(part[0])
+    return model
+
+
 def build_dense_workers(cfg: EngineConfig, X: torch.Tensor, y: torch.Tensor,
                         devices: Optional[List[torch.device]] = None
                         ) -> List[Worker]:

@@ -453,6 +453,94 @@ PYBIND11_MODULE(_hip_core, m) {
           check(hipGetLastError(), "eval_curve_csr launch");
         });
 
+  // Column statistics and standardisation (csrc/col_stats.h). The dense
+  // scratch is sized by col_stats_geom(); out_f64 is [6][d] fp64 (mean, M2,
+  // min, max, sum |x|, sum x^2) and out_nnz [d] int64.
+  m.def("col_stats_geom", [](uintptr_t X, long n_rows, int d, int x_is_bf16) {
+    long long v[5] = {0};
+    query_col_stats_geom(n_rows, d,
+                         query_col_stats_vec((const void*)X, d, x_is_bf16),
+                         v);
+    py::dict e;
+    e["vec"] = v[0];
+    e["grid_x"] = v[1];
+    e["grid_y"] = v[2];
+    e["row_slots"] = v[3];
+    e["rows_per_block"] = v[4];
+    return e;
+  });
+  m.def("col_stats_dense",
+        [](uintptr_t X, long n_rows, int d, int x_is_bf16, uintptr_t part_f64,
+           uintptr_t part_mm, uintptr_t part_nnz, uintptr_t out_f64,
+           uintptr_t out_nnz, uintptr_t stream) {
+          launch_col_stats_dense((const void*)X, n_rows, d, x_is_bf16,
+                                 (double*)part_f64, (float*)part_mm,
+                                 (int*)part_nnz, (double*)out_f64,
+                                 (long long*)out_nnz, (hipStream_t)stream);
+          check(hipGetLastError(), "col_stats_dense launch");
+        });
+  m.def("col_stats_csr",
+        [](uintptr_t indptr, uintptr_t indices, uintptr_t values, long n_rows,
+           int d, long nnz_hint, int v_is_bf16, uintptr_t sums,
+           uintptr_t ints, uintptr_t out_f64, uintptr_t out_nnz,
+           uintptr_t stream) {
+          launch_col_stats_csr((const int*)indptr, (const int*)indices,
+                               (const void*)values, n_rows, d, nnz_hint,
+                               v_is_bf16, (double*)sums, (unsigned int*)ints,
+                               (double*)out_f64, (long long*)out_nnz,
+                               (hipStream_t)stream);
+          check(hipGetLastError(), "col_stats_csr launch");
+        });
+  m.def("scale_dense",
+        [](uintptr_t X, uintptr_t mean, uintptr_t factor, long n_rows, int d,
+           int x_is_bf16, int with_mean, uintptr_t stream) {
+          launch_scale_dense((void*)X, (const float*)mean,
+                             (const float*)factor, n_rows, d, x_is_bf16,
+                             with_mean, (hipStream_t)stream);
+          check(hipGetLastError(), "scale_dense launch");
+        });
+  m.def("scale_csr",
+        [](uintptr_t indices, uintptr_t values, uintptr_t factor, long nnz,
+           int d, int v_is_bf16, uintptr_t stream) {
+          launch_scale_csr((const int*)indices, (void*)values,
+                           (const float*)factor, nnz, d, v_is_bf16,
+                           (hipStream_t)stream);
+          check(hipGetLastError(), "scale_csr launch");
+        });
+  // Compiled register / scratch / LDS use and blocks per CU of every
+  // col_stats.h kernel, by name (LDS: the largest dynamic size a launch
+  // takes).
+  m.def("col_stats_kernel_info", []() {
+    py::dict out;
+    const int n = query_col_stats_kernel_count();
+    for (int k = 0; k < n; ++k) {
+      int v[8] = {0};
+      check((hipError_t)query_col_stats_kernel(k, v),
+            "col_stats_kernel_info");
+      py::dict e;
+      e["num_regs"] = v[0];
+      e["local_size_bytes"] = v[1];
+      e["lds_bytes"] = v[2];
+      e["max_active_blocks_per_cu"] = v[3];
+      const std::string xt = v[5] ? "bf16" : "float";
+      const std::string vec = std::to_string(v[6]);
+      std::string name;
+      switch (v[4]) {
+        case 0: name = "col_stats_dense_kernel<" + xt + "," + vec + ">"; break;
+        case 1: name = "col_stats_finish_kernel"; break;
+        case 2: name = "col_stats_csr_kernel<" + xt + ">"; break;
+        case 3: name = "col_stats_csr_finish_kernel"; break;
+        case 4:
+          name = "scale_dense_kernel<" + xt + "," + vec + "," +
+                 (v[7] ? "true" : "false") + ">";
+          break;
+        default: name = "scale_csr_kernel<" + xt + ">"; break;
+      }
+      out[py::str(name)] = e;
+    }
+    return out;
+  });
+
   register_libsvm(m);
   register_native_engine(m);
   register_resident_engine(m);

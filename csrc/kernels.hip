@@ -1994,3 +1994,9 @@ void launch_alpha_gather(float* a_dst, const float* a_src, const int* rows,
 // Threshold sweep of the evaluation (ROC / PR points in one pass): the K9
 // scoring walks with an LDS histogram per iterate.
 #include "eval_curve.h"
+
+// ---------------------------------------------------------------- K11
+// Column statistics (MLlib colStats) and in-place feature standardisation:
+// streaming passes built on to_f32, with_const / with_bool and eval.h's
+// with_xt.
+#include "col_stats.h"

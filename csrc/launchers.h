@@ -220,4 +220,32 @@ void launch_eval_curve_csr(const int* indptr, const int* indices,
 // as query_eval_kernel, query_eval_kernel_count() instantiations
 int query_eval_curve_kernel(int idx, int* out);
 
+// ---- column statistics and standardisation (defined in col_stats.h) -----
+
+// out[5], see the definition
+void query_col_stats_geom(long n_rows, int d, int vec, long long* out);
+int query_col_stats_vec(const void* X, int d, int x_is_bf16);
+
+void launch_col_stats_dense(const void* X, long n_rows, int d, int x_is_bf16,
+                            double* part_f64, float* part_mm, int* part_nnz,
+                            double* out_f64, long long* out_nnz,
+                            hipStream_t stream);
+
+void launch_col_stats_csr(const int* indptr, const int* indices,
+                          const void* values, long n_rows, int d,
+                          long nnz_hint, int v_is_bf16, double* sums,
+                          unsigned int* ints, double* out_f64,
+                          long long* out_nnz, hipStream_t stream);
+
+void launch_scale_dense(void* X, const float* mean, const float* factor,
+                        long n_rows, int d, int x_is_bf16, int with_mean,
+                        hipStream_t stream);
+
+void launch_scale_csr(const int* indices, void* values, const float* factor,
+                      long nnz, int d, int v_is_bf16, hipStream_t stream);
+
+// out[8], see the definition
+int query_col_stats_kernel(int idx, int* out);
+int query_col_stats_kernel_count();
+
 }  // extern "C"
